@@ -23,7 +23,13 @@ Multi-GPU (no data-path collective):
   launch) so small per-rank shards are not launch-bound.  ``--gather`` also
   gathers the rows to rank 0 each call (the one real exchange of this mode).
 
-Companions on the same line (never ``value``), run by every rank in multi-GPU
+A plain run sets up, warms up, times ``--steps`` steps and prints the line
+(``roofline`` holds the main kernel's event timing from the timed region).
+``--dump-outputs DIR`` also writes what the last timed step left for a caller
+(see dump_outputs).  Everything else is behind ``--full``: the copy ceiling and
+the PMC / SQ records of ``roofline``, ``cpu_baseline`` and the companions.
+
+Companions on the same line with ``--full`` (never ``value``), run by every rank in multi-GPU
 runs with per-rank times: ``f32`` (the headline on float32 IQ), ``config2``
 (16 K cf32 Hann), ``config4`` / ``config4_f32`` (the shard workload on s8 and cf32
 input), ``config5`` (a 1 M-point
@@ -97,6 +103,12 @@ def parse(argv=None):
                    help="HIP-event timing of every K-th main-kernel launch in the timed region (1 = all)")
     p.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     p.add_argument("--dry-run", action="store_true", help="no GPU: launcher / barrier / timing path only (gloo)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: copy ceiling, PMC / SQ records, CPU baseline and "
+                        "the companion workloads (the --*-steps / --cpu-seconds / --host-fed-calls options)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one left for a caller as DIR/<name>.npy "
+                        "(float32; a fixed seeded sample of the rows, at most 64 MB in all)")
     a = p.parse_args(argv)
     if a.fft_size == 0:
         a.fft_size = 65536 if a.mode == "streams" else 8192
@@ -219,9 +231,37 @@ def timed(ranks, step, steps, warmup):
     return max(per), per
 
 
-def run_streams(args, ranks, fmt, steps, warmup, seed):
+DUMP_BUDGET = 64 * 10 ** 6  # bytes over all ranks and arrays of --dump-outputs
+DUMP_SEED = 20240
+
+
+def sample_rows(total, n, budget):
+    """Sorted indices of a fixed, seeded sample of `total` rows of n float32 values that fits
+    `budget` bytes (every row when they all fit)."""
+    import numpy as np
+
+    k = max(1, min(total, budget // (4 * n)))
+    if k >= total:
+        return np.arange(total)
+    return np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(total, k, replace=False))
+
+
+def dump_outputs(ranks, directory, arrays):
+    """--dump-outputs: this rank's arrays as DIR/<name>.npy (DIR/<name>_rank<r>.npy past one rank)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + (f"_rank{ranks.rank}" if ranks.world > 1 else "") + ".npy"), a)
+
+
+def run_streams(args, ranks, fmt, steps, warmup, seed, dump=None):
     """Config 3 per rank: one stream, B frames per call into ring + peak + EMA.
-    Returns (slowest seconds, per-rank seconds, main-kernel ms per launch, kernel name)."""
+    Returns (slowest seconds, per-rank seconds, main-kernel ms per launch, kernel name).
+    dump: a dict that receives the state a caller reads after the last timed step (ring rows
+    in storage order, a seeded sample of them past the budget, peak-hold, EMA / boxcar)."""
     import rfanalyzer_amd
 
     torch = ranks.torch
@@ -239,6 +279,7 @@ def run_streams(args, ranks, fmt, steps, warmup, seed):
     if args.state_cus:
         eng.set_pipelined(args.state_cus)
     pool = make_pool(torch, n, frames, fmt, args.pool_mib, seed, ranks.device)
+    ranks.sync()  # the pool is written on torch's stream; with --state-cus the engine runs on another
     eng.set_tuning(100_000_000, 20_000_000)
     ctr = [0]
 
@@ -264,16 +305,30 @@ def run_streams(args, ranks, fmt, steps, warmup, seed):
     sampling[0] = False
     ms1, l1 = eng.kernel_time()
     name = eng.main_kernel_name()
+    if dump is not None:
+        eng.synchronize()
+        budget = DUMP_BUDGET // ranks.world - 8 * n  # the two state rows beside the ring sample
+        if args.ring_rows > 0:
+            ring, _, _ = eng.ring()
+            dump["ring_rows"] = ring[sample_rows(ring.shape[0], n, budget)]
+            del ring
+        if not args.no_peak:
+            dump["peaks"] = eng.peaks()
+        if args.avg == "ema":
+            dump["ema"] = eng.ema()
+        elif args.avg == "boxcar":
+            dump["boxcar"] = eng.boxcar()
     eng.close()
     del pool
     return slow, per, (ms1 - ms0) / max(1, l1 - l0), name
 
 
-def run_shard(args, ranks, steps, warmup):
+def run_shard(args, ranks, steps, warmup, dump=None):
     """Config 4: every batch of `frames` independent frames is split over the ranks
     (sharding.frame_range); a call enqueues `batches_per_call` consecutive batches of
     this rank's frames (rfa_process_batches, one launch); rows stay on each rank's
-    device unless --gather.  Returns (slowest s, per-rank s, kernel ms, name, range, batches per call)."""
+    device unless --gather.  Returns (slowest s, per-rank s, kernel ms, name, range, batches per call).
+    dump: a dict that receives the last call's rows of this rank (a seeded sample past the budget)."""
     import rfanalyzer_amd
     from rfanalyzer_amd import sharding
 
@@ -329,6 +384,11 @@ def run_shard(args, ranks, steps, warmup):
     sampling[0] = False
     ms1, l1 = eng.kernel_time()
     name = eng.main_kernel_name()
+    if dump is not None and mine:
+        eng.synchronize()
+        torch.cuda.synchronize()
+        idx = sample_rows(kb * mine, n, DUMP_BUDGET // ranks.world)
+        dump["rows"] = rows[:kb * mine * n].view(kb * mine, n)[torch.as_tensor(idx, device=ranks.device)].cpu().numpy()
     eng.close()
     return slow, per, (ms1 - ms0) / max(1, l1 - l0), name, (s, e), kb
 
@@ -701,16 +761,21 @@ def main():
     n, frames, fmt, calls = args.fft_size, args.frames, args.format, args.calls_per_step
     result = {"metric": METRIC}
     kb = 1
+    dump = {} if args.dump_outputs else None
     if args.dry_run:
         slow, per = timed(ranks, lambda k: time.sleep(0.001 * (1 + ranks.rank)), args.steps, args.warmup)
         kernel_ms, kernel_name, span = 0.0, "dry-run", None
         mine = frames
     elif args.mode == "streams":
-        slow, per, kernel_ms, kernel_name = run_streams(args, ranks, fmt, args.steps, args.warmup, 3 + ranks.rank)
+        slow, per, kernel_ms, kernel_name = run_streams(args, ranks, fmt, args.steps, args.warmup, 3 + ranks.rank,
+                                                         dump)
         mine = frames
     else:
-        slow, per, kernel_ms, kernel_name, span, kb = run_shard(args, ranks, args.steps, args.warmup)
+        slow, per, kernel_ms, kernel_name, span, kb = run_shard(args, ranks, args.steps, args.warmup, dump)
         mine = (span[1] - span[0]) * kb
+    if dump is not None:
+        dump_outputs(ranks, args.dump_outputs, dump)
+        del dump
 
     batches = kb if args.mode == "shard" else 1
     total_frames = (ranks.world if args.mode == "streams" else 1) * frames * batches * calls * args.steps
@@ -756,7 +821,7 @@ def main():
                           "timing": f"HIP events on the handle stream around every {max(1, args.profile_every)}-th "
                                     "main-kernel launch of the timed region"}
     single = ranks.rank == 0 and ranks.world == 1 and not args.dry_run
-    if single:
+    if single and args.full:
         tr, src = pmc_traffic(args, fmt, n, mine)
         result["roofline"]["traffic"] = tr
         result["roofline"]["traffic_source"] = src
@@ -764,17 +829,18 @@ def main():
         if va is not None:
             result["roofline"]["valu"] = va
     if ranks.rank == 0 and not args.dry_run:
-        gbps, ok = copy_ceiling(torch, ranks.device)
-        result["roofline"]["copy_GBps"] = gbps
-        result["roofline"]["copy_kernel"] = "rfa_stream_copy (librfa float4 copy)" + ("" if ok else " MISMATCH")
-        result["roofline"]["frac_of_copy"] = round(achieved / gbps, 4)
+        if args.full:
+            gbps, ok = copy_ceiling(torch, ranks.device)
+            result["roofline"]["copy_GBps"] = gbps
+            result["roofline"]["copy_kernel"] = "rfa_stream_copy (librfa float4 copy)" + ("" if ok else " MISMATCH")
+            result["roofline"]["frac_of_copy"] = round(achieved / gbps, 4)
         if args.mode == "streams":
             # step level: every byte the step must move (raw in, ring row out, EMA + peak read+write) / step time
             step_bytes = frames * n * (s_in + 4) + 16 * n
             result["roofline"]["step_frac"] = round(step_bytes * calls * args.steps / slow / 1e9 / HBM_PEAK_GBPS, 4)
-    if args.mode == "streams":
+    if args.full and args.mode == "streams":
         companions(args, ranks, result)
-    if ranks.rank == 0 and ranks.world == 1 and args.cpu_seconds > 0 and args.mode == "streams":
+    if args.full and ranks.rank == 0 and ranks.world == 1 and args.cpu_seconds > 0 and args.mode == "streams":
         result["cpu_baseline"] = cpu_baseline(args, n, args.cpu_seconds)
         result["cpu_baseline"]["config1"] = config1_replay(not args.dry_run)
     if ranks.rank == 0:

@@ -1,9 +1,9 @@
 #!/bin/bash
-# Copy the judged records of one r04_evidence.sh / final_evidence.sh call from gpurun_out/ into
+# Copy the judged records of one r04_evidence.sh / final_evidence.sh call from $EVIDENCE_DIR (evidence/) into
 # profiles/TAG/ (tracked).  usage: scripts/collect_evidence.sh TAG
 set -eu
 cd "$(dirname "$0")/.."
-T=$1; D=profiles/$T; G=gpurun_out
+T=$1; D=profiles/$T; G=${EVIDENCE_DIR:-evidence}
 mkdir -p $D
 cp $G/bench_$T.json $D/bench.json
 cp $G/pytest_gpu_$T.log $D/pytest_gpu.txt

@@ -11,4 +11,4 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_state.py tests/test_gpu_par
 bash scripts/ab_kbench.sh gpurun_out/r05b_ab.txt "--sizes 65536 --formats s8,f32 --samples 32768000 --state" \
   "base|RFA_LIB=abv/librfa_base.so" "igs_off|RFA_LIB=abv/librfa_igs.so RFA_IGS=0" "igs_on|RFA_LIB=abv/librfa_igs.so" \
   "base2|RFA_LIB=abv/librfa_base.so" "igs_on2|RFA_LIB=abv/librfa_igs.so" "pf|RFA_LIB=abv/librfa_pf.so" "pf_off|RFA_LIB=abv/librfa_pf.so RFA_IGS=0" &&
-timeout -k 10 600 python -u bench.py --cpu-seconds 3 > gpurun_out/r05b_bench.json 2> gpurun_out/r05b_bench.err; rc=$?; tail -c 400 gpurun_out/r05b_bench.json; exit $rc
+{ O=${EVIDENCE_DIR:-evidence}; mkdir -p $O; timeout -k 10 600 python -u bench.py --full --cpu-seconds 3 > $O/r05b_bench.json 2> $O/r05b_bench.err; }; rc=$?; tail -c 400 $O/r05b_bench.json; exit $rc

@@ -15,7 +15,7 @@ V=()
 for i in 1 2 3; do V+=("base$i|RFA_LIB=abv/librfa_base.so" "own1_$i|RFA_LIB=abv/librfa_own1.so"); done
 bash scripts/ab_kbench.sh $O/kbench.txt "--sizes 8192,16384,32768 --formats s8,u8,s16 --samples 32768000 --iters 30" "${V[@]}" > /dev/null || exit 1
 grep -E "^==|N=" $O/kbench.txt
-B="--steps 10 --warmup 2 --f32-steps 0 --c5-steps 0 --c2-steps 0 --demod-steps 0 --host-fed-calls 0 --cpu-seconds 0"
+B="--full --steps 10 --warmup 2 --f32-steps 0 --c5-steps 0 --c2-steps 0 --demod-steps 0 --host-fed-calls 0 --cpu-seconds 0"
 for i in 1 2 3; do
   for v in base own1; do
     RFA_LIB=abv/librfa_$v.so timeout -k 10 180 python bench.py $B > $O/c4_${v}_$i.json 2> $O/c4_${v}_$i.err || { echo "c4 $v rc=$?"; tail -3 $O/c4_${v}_$i.err; exit 1; }

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/r06r_ab
 mkdir -p $O
 export TMPDIR=/tmp
-B="--steps 4 --warmup 2 --f32-steps 10 --c5-steps 0 --c2-steps 0 --c4-steps 0 --demod-steps 0 --host-fed-calls 0 --cpu-seconds 0"
+B="--full --steps 4 --warmup 2 --f32-steps 10 --c5-steps 0 --c2-steps 0 --c4-steps 0 --demod-steps 0 --host-fed-calls 0 --cpu-seconds 0"
 for i in 1 2 3 4; do
   for v in base ownq; do
     RFA_LIB=abv/librfa_$v.so timeout -k 10 180 python bench.py $B > $O/${v}_$i.json 2> $O/${v}_$i.err || { echo "$v rc=$?"; tail -3 $O/${v}_$i.err; exit 1; }

@@ -11,7 +11,7 @@ RFA_LIB=abv/librfa_ownb.so timeout -k 10 300 python -u -m pytest tests/test_gpu_
     -x -q --timeout 120 --timeout-method thread -m gpu -k "f32 or config2 or config5 or 1048576 or large or 262144 or 524288" \
     > $O/pytest_ownb.txt 2>&1 || { echo "pytest rc=$?"; tail -30 $O/pytest_ownb.txt; exit 1; }
 echo "ownb: $(tail -1 $O/pytest_ownb.txt)"
-B="--steps 2 --warmup 1 --f32-steps 0 --c5-steps 10 --c2-steps 10 --c4-steps 4 --demod-steps 0 --host-fed-calls 0 --cpu-seconds 0"
+B="--full --steps 2 --warmup 1 --f32-steps 0 --c5-steps 10 --c2-steps 10 --c4-steps 4 --demod-steps 0 --host-fed-calls 0 --cpu-seconds 0"
 for i in 1 2 3 4; do
   for v in base ownb; do
     RFA_LIB=abv/librfa_$v.so timeout -k 10 240 python bench.py $B > $O/${v}_$i.json 2> $O/${v}_$i.err || { echo "$v rc=$?"; tail -3 $O/${v}_$i.err; exit 1; }
