@@ -439,6 +439,87 @@ RFA_API int rfa_resampler_design(int32_t output_rate, int32_t input_rate, int32_
 RFA_API int rfa_lowpass_taps(float gain, float sample_rate, float cutoff, float transition, float attenuation,
                              int32_t max_taps, float *taps, size_t capacity, int32_t *num_taps);
 
+/* ------------------------------------------------------------------------
+ * Demodulator: quadrature-rate IQ (what rfa_ddc_process writes, planar float
+ * on the device) -> 48 kHz float audio.  One handle is one Demodulator with
+ * its AudioSink.  Replaces (app paths as above):
+ *   Demodulator.run's per-packet chain           rfa_demod_process()
+ *     analyzer/Demodulator.kt:151-187
+ *   applyUserFilter / FirFilter.filter           rfa_demod_process()
+ *     analyzer/Demodulator.kt:215-240, dsp/FirFilter.kt:63-107
+ *   demodulateFM / AM / SSB / CW                 rfa_demod_process()
+ *     analyzer/Demodulator.kt:251-403
+ *   ComplexFirFilter.filter                      rfa_demod_process()
+ *     dsp/ComplexFirFilter.java:123-170
+ *   ComplexFirFilter.createBandPass              rfa_bandpass_taps()  (host only)
+ *     dsp/ComplexFirFilter.java:186-278
+ *   AudioSink's filters and applyAudioFilter     rfa_demod_process()
+ *     analyzer/AudioSink.java:94-97,215-237, dsp/FirFilter.kt:121-163
+ *   DemodulationMode's rates and widths          rfa_demod_mode_info() (host only)
+ *     analyzer/Demodulator.kt:52-61
+ * A call carries n_samples split into packets of packet_samples (the last one
+ * may be short; 0 = one packet; n_samples 0 = one empty packet) and equals the
+ * reference run packet by packet: AM's mean and the AGC are per-packet
+ * quantities.  The filters' delay lines and counters, carryOverSamples and
+ * lastMax carry over between packets, calls and mode changes as there.
+ * AM, LSB, USB and CW audio is bit-exact against the restated chain; FM differs
+ * only where the device's double atan2 rounds differently from the host's.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_demod rfa_demod;
+enum rfa_demod_mode { RFA_DEMOD_OFF, RFA_DEMOD_AM, RFA_DEMOD_NFM, RFA_DEMOD_WFM, RFA_DEMOD_LSB, RFA_DEMOD_USB,
+                      RFA_DEMOD_CW };
+enum rfa_demod_taps { RFA_DEMOD_TAPS_USER, RFA_DEMOD_TAPS_BANDPASS, RFA_DEMOD_TAPS_AUDIO1, RFA_DEMOD_TAPS_AUDIO2 };
+
+/* Host only: quadrature rate and channel width limits of a mode (any pointer may be NULL). */
+RFA_API int rfa_demod_mode_info(int mode, int32_t *quadrature_rate, int32_t *min_width, int32_t *max_width,
+                                int32_t *default_width);
+/* Host only: ComplexFirFilter.createBandPass's taps with its float/double
+ * promotions.  RFA_ERR_INVALID where it returns null; *num_taps is always set,
+ * re/im (either may be NULL) written when capacity suffices. */
+RFA_API int rfa_bandpass_taps(float gain, float fs, float lo, float hi, float transition, float attenuation,
+                              float *re, float *im, size_t capacity, int32_t *num_taps);
+/* A Demodulator with demodulationMode = mode (channel width = the mode's
+ * default, volume 1) and a fresh AudioSink.  RFA_ERR_NODEVICE without a GPU. */
+RFA_API int rfa_demod_create(int device, int mode, rfa_demod **out);
+RFA_API int rfa_demod_destroy(rfa_demod *d);
+RFA_API const char *rfa_demod_last_error(const rfa_demod *d);
+/* demodulationMode's setter (Demodulator.kt:96-100): width := the mode's
+ * default; every filter, AGC and carry-over state is kept. */
+RFA_API int rfa_demod_set_mode(rfa_demod *d, int mode);
+RFA_API int rfa_demod_get_mode(const rfa_demod *d, int32_t *mode);
+/* channelWidth's setter: coerced into the mode's [min, max] (Demodulator.kt:75).
+ * The user filter is rebuilt by the next packet when its cut-off differs (:217). */
+RFA_API int rfa_demod_set_channel_width(rfa_demod *d, int32_t w);
+RFA_API int rfa_demod_get_channel_width(const rfa_demod *d, int32_t *w);
+RFA_API int rfa_demod_set_volume(rfa_demod *d, float v);      /* audioVolumeLevel */
+/* enable 0: the output is the Demodulator's audioBuffer after the volume, at
+ * the packet rate, and the AudioSink's filters see nothing. */
+RFA_API int rfa_demod_set_audio_sink(rfa_demod *d, int enable);
+/* Device pointers, asynchronous on the handle's stream.  *n_audio is computed on
+ * the host; RFA_ERR_SIZE if it exceeds capacity (nothing is consumed then).
+ * RFA_DEMOD_OFF: no output and no state change. */
+RFA_API int rfa_demod_process(rfa_demod *d, const float *re, const float *im, size_t n_samples,
+                              size_t packet_samples, float *audio, size_t capacity, size_t *n_audio);
+/* Same with host buffers; synchronous. */
+RFA_API int rfa_demod_process_host(rfa_demod *d, const float *re, const float *im, size_t n_samples,
+                                   size_t packet_samples, float *audio, size_t capacity, size_t *n_audio);
+/* Exactly what the next rfa_demod_process of n_samples would write. */
+RFA_API int rfa_demod_max_outputs(const rfa_demod *d, size_t n_samples, size_t *n);
+/* which: rfa_demod_taps.  The user and band-pass filters exist once a packet
+ * built them (0 taps before); im is zero for the real filters. */
+RFA_API int rfa_demod_get_taps(const rfa_demod *d, int which, float *re, float *im, size_t capacity,
+                               int32_t *num_taps, int32_t *decimation);
+/* lastMax and carryOverSamplesRe/Im; drains the stream. */
+RFA_API int rfa_demod_get_state(rfa_demod *d, float *last_max, float *carry_re, float *carry_im);
+/* The signal path of a freshly created Demodulator + AudioSink: no user or
+ * band-pass filter, zero carry-over and lastMax, empty audio delay lines.
+ * Mode, width, volume and the audio-sink switch stay. */
+RFA_API int rfa_demod_reset(rfa_demod *d);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_demod_set_stream(rfa_demod *d, void *stream);
+RFA_API int rfa_demod_get_stream(const rfa_demod *d, void **stream);
+RFA_API int rfa_demod_synchronize(rfa_demod *d);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@ reference's interfaces for this path:
     SpectrumEngine.draw_preprocess, scanner   AnalyzerSurface.drawPreprocessing, MainViewModel scanner
     recording                  Scheduler recording branch, file names, replay metadata
     demod.FrontEnd             IQConverter.mixPacketIntoSamplePacket + Decimator / Resampler
+    demod.Demodulator          analyzer/Demodulator.kt + AudioSink.java: AM/FM/SSB/CW to 48 kHz audio
+    demod.Receiver             FrontEnd chained into Demodulator, raw IQ bytes to audio
     scheduler.Scheduler        analyzer/Scheduler.kt packet fan-out
 
 There is no CPU fallback: without librfa.so or a HIP device, calls raise.

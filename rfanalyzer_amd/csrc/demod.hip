@@ -1,0 +1,954 @@
+// demod.hip -- the demodulator proper on gfx950: quadrature-rate IQ (what
+// rfa_ddc_process writes) -> 48 kHz float audio.  Paths relative to
+// app/src/main/java/com/mantz_it/rfanalyzer/.
+//
+// Per packet the reference runs (analyzer/Demodulator.kt:151-187)
+//   applyUserFilter (215-240)  ->  demodulateAM/FM/SSB/CW (251-403)  ->  volume
+//   ->  AudioSink.applyAudioFilter (analyzer/AudioSink.java:215-237).
+// Here one call carries any number of packets and runs four kernels:
+//   1. demod_stage1_kernel: a workgroup owns 256 consecutive pre-gain outputs,
+//      stages the inputs they depend on (plus halo and the carried history)
+//      into LDS, writes the user-filtered samples back into LDS and runs the
+//      mode's step from there (|x|^2, the discriminator, or the complex
+//      band-pass FIR of dsp/ComplexFirFilter.java:123-170);
+//   2. demod_packet_kernel: one wave per packet takes the packet's maximum and,
+//      for AM, its sum in index order (loads coalesced, adds by one lane);
+//   3. demod_state_kernel: one workgroup resolves the lastMax recurrence over
+//      the call's packets and writes every piece of state the next call needs;
+//   4. demod_audio_kernel: gain by packet index, volume, and the AudioSink's
+//      one or two decimating FIRs over the continuous stream, through LDS.
+// All filters are closed forms of the reference's counters: output n of a
+// FirFilter built `in` samples ago has its newest input at n*D + off (off = D-1,
+// or 1 for D = 1: decimationCounter starts at 1).  Output counts are computed on
+// the host.  Products and sums are separately rounded in the reference's order.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/rfa.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kTile = 256;               // outputs per workgroup
+constexpr int kMaxUserTaps = 32;         // the user filter has 27
+constexpr int kMaxBandTaps = 192;        // the band-pass filters have 181
+constexpr int kMaxAudioTaps = 16;        // audioFilter1 has 9, audioFilter2 13
+constexpr int kA1Dec = 2, kA2Dec = 4;    // AudioSink.java:94-96
+constexpr int kAudioRate = 48000;
+
+// device state, floats (two copies: a call reads one and writes the other)
+constexpr int ST_UF_RE = 0, ST_UF_IM = ST_UF_RE + kMaxUserTaps;
+constexpr int ST_BP_RE = ST_UF_IM + kMaxUserTaps, ST_BP_IM = ST_BP_RE + kMaxBandTaps;
+constexpr int ST_A1 = ST_BP_IM + kMaxBandTaps, ST_A2 = ST_A1 + kMaxAudioTaps;
+constexpr int ST_CARRY = ST_A2 + kMaxAudioTaps, ST_LMAX = ST_CARRY + 2;
+constexpr int ST_SIZE = 512;
+static_assert(ST_LMAX < ST_SIZE, "state layout");
+// device taps
+constexpr int TP_UF = 0, TP_BPR = TP_UF + kMaxUserTaps, TP_BPI = TP_BPR + kMaxBandTaps;
+constexpr int TP_A1 = TP_BPI + kMaxBandTaps, TP_A2 = TP_A1 + kMaxAudioTaps, TP_SIZE = TP_A2 + kMaxAudioTaps;
+
+enum { kKindAm = 0, kKindFm = 1, kKindBand = 2 };
+
+struct DemodLaunch {
+    const float *re, *im;          // this call's input, planar
+    long long n, ps, K;            // samples, packet size (>= 1), packets (>= 1)
+    const float *st;               // state before the call
+    float *nst;                    // state after it
+    const float *taps;
+    int kind;
+    int Tu, Tb, T1, T2;            // taps of the user / band-pass / audio filters
+    int Db, offb;                  // band-pass decimation and first-output offset (AM/FM: 1, 0)
+    int skip;                      // 1: the user filter is fresh, its first input gives no output
+    long long F;                   // user-filtered samples of this call: filtered f <-> input f + skip
+    long long bp_in0, bp_out0;     // band-pass inputs / outputs before this call (AM/FM: 0, 0)
+    long long npre;                // pre-gain values of this call
+    float qgain, volume;
+    int agc;                       // AM, SSB, CW
+    int sink;                      // 0: none, 1: audioFilter1, 2: audioFilter1 then audioFilter2
+    long long a1_in0, a1_out0, ny1, a2_in0, a2_out0, n_audio;
+    float *pre, *pk_max, *pk_avg, *pk_gain, *out;
+};
+
+// ---------------------------------------------------------------- device helpers
+
+__device__ __forceinline__ void in_at(const DemodLaunch &a, long long i, float &re, float &im) {
+    if (i < 0) {
+        re = a.st[ST_UF_RE + a.Tu - 1 + i];
+        im = a.st[ST_UF_IM + a.Tu - 1 + i];
+    } else {
+        re = a.re[i];
+        im = a.im[i];
+    }
+}
+
+// user-filtered sample f >= 0 of this call, straight from memory (FirFilter.kt:86-95)
+__device__ void filt_at(const DemodLaunch &a, long long f, float &re, float &im) {
+    float sr = 0.0f, si = 0.0f;
+    for (int k = 0; k < a.Tu; k++) {
+        float xr, xi;
+        in_at(a, f + a.skip - k, xr, xi);
+        const float t = a.taps[TP_UF + k];
+        sr = sr + t * xr;
+        si = si + t * xi;
+    }
+    re = sr;
+    im = si;
+}
+
+// user-filtered index of pre-gain value m: the band-pass output's newest input
+__device__ __forceinline__ long long fidx(const DemodLaunch &a, long long m) {
+    return (a.bp_out0 + m) * a.Db + a.offb - a.bp_in0;
+}
+
+// number of pre-gain values whose input index is below X
+__device__ __forceinline__ long long pre_lower(const DemodLaunch &a, long long X) {
+    const long long R = X - a.skip - a.offb + a.bp_in0;
+    if (R <= 0) return 0;
+    const long long c = (R + a.Db - 1) / a.Db - a.bp_out0;
+    return c < 0 ? 0 : (c > a.npre ? a.npre : c);
+}
+
+// value q of the stream the AudioSink sees (after gain and volume); q < 0: audioFilter1's delay line
+__device__ __forceinline__ float v_at(const DemodLaunch &a, long long q) {
+    if (q < 0) return a.st[ST_A1 + a.T1 - 1 + q];
+    float x = a.pre[q];
+    if (a.agc) {
+        long long p = (fidx(a, q) + a.skip) / a.ps;
+        if (p > a.K - 1) p = a.K - 1;
+        if (a.kind == kKindAm) x = (x - a.pk_avg[p]) * a.pk_gain[p];
+        else x = x * a.pk_gain[p];
+    }
+    return x * a.volume;
+}
+
+// newest audioFilter1 input (call-relative) of its output r of this call
+__device__ __forceinline__ long long c1_of(const DemodLaunch &a, long long r) {
+    return (a.a1_out0 + r) * kA1Dec + (kA1Dec - 1) - a.a1_in0;
+}
+
+// audioFilter1 output r of this call; r < 0: audioFilter2's delay line
+__device__ float y1_at(const DemodLaunch &a, long long r) {
+    if (r < 0) return a.st[ST_A2 + a.T2 - 1 + r];
+    const long long c = c1_of(a, r);
+    float s = 0.0f;
+    for (int k = 0; k < a.T1; k++) s = s + a.taps[TP_A1 + k] * v_at(a, c - k);
+    return s;
+}
+
+// ---------------------------------------------------------------- kernel 1
+
+constexpr int kFlMax = (kTile - 1) * 2 + kMaxBandTaps;   // user-filtered run of a tile (decimation <= 2)
+constexpr int kInMax = kFlMax + kMaxUserTaps;
+
+__global__ __launch_bounds__(kTile) void demod_stage1_kernel(DemodLaunch a) {
+    __shared__ float xr[kInMax], xi[kInMax], fr[kFlMax], fi[kFlMax];
+    __shared__ float tu[kMaxUserTaps], tbr[kMaxBandTaps], tbi[kMaxBandTaps];
+    const int tid = threadIdx.x;
+    const long long m0 = (long long)blockIdx.x * kTile;
+    const int nloc = (int)min((long long)kTile, a.npre - m0);
+    if (tid < a.Tu) tu[tid] = a.taps[TP_UF + tid];
+    if (a.kind == kKindBand && tid < a.Tb) {
+        tbr[tid] = a.taps[TP_BPR + tid];
+        tbi[tid] = a.taps[TP_BPI + tid];
+    }
+    const long long f_first = fidx(a, m0), f_last = fidx(a, m0 + nloc - 1);
+    const int halo = a.kind == kKindBand ? a.Tb - 1 : (a.kind == kKindFm ? 1 : 0);
+    const long long flo = f_first - halo, fclo = flo < 0 ? 0 : flo;
+    const int nhist = (int)(fclo - flo);                 // samples older than this call
+    const int ncomp = (int)(f_last - fclo + 1);          // user-filtered samples to compute
+    const int nin = ncomp + a.Tu - 1;
+    const long long ilo = fclo + a.skip - (a.Tu - 1);
+    for (int i = tid; i < nin; i += kTile) {
+        float r, s;
+        in_at(a, ilo + i, r, s);
+        xr[i] = r;
+        xi[i] = s;
+    }
+    for (int j = tid; j < nhist; j += kTile) {
+        const long long f = flo + j;                      // < 0
+        if (a.kind == kKindBand) {
+            fr[j] = a.st[ST_BP_RE + a.Tb - 1 + f];
+            fi[j] = a.st[ST_BP_IM + a.Tb - 1 + f];
+        } else {                                          // FM: carryOverSamples
+            fr[j] = a.st[ST_CARRY];
+            fi[j] = a.st[ST_CARRY + 1];
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < ncomp; j += kTile) {
+        float sr = 0.0f, si = 0.0f;
+        const float *pr = xr + j + a.Tu - 1, *pi = xi + j + a.Tu - 1;
+        for (int k = 0; k < a.Tu; k++) {
+            sr = sr + tu[k] * pr[-k];
+            si = si + tu[k] * pi[-k];
+        }
+        fr[nhist + j] = sr;
+        fi[nhist + j] = si;
+    }
+    __syncthreads();
+    if (tid >= nloc) return;
+    const long long m = m0 + tid;
+    const int j = (int)(fidx(a, m) - flo);
+    float v;
+    if (a.kind == kKindAm) {
+        v = fr[j] * fr[j] + fi[j] * fi[j];
+    } else if (a.kind == kKindFm) {
+        const float cr = fr[j] * fr[j - 1] + fi[j] * fi[j - 1];
+        const float ci = fi[j] * fr[j - 1] - fr[j] * fi[j - 1];
+        v = a.qgain * (float)atan2((double)ci, (double)cr);
+    } else {
+        float s = 0.0f;                                   // only the real part is ever used
+        for (int k = 0; k < a.Tb; k++) s = s + (tbr[k] * fr[j - k] - tbi[k] * fi[j - k]);
+        v = s;
+    }
+    a.pre[m] = v;
+}
+
+// ---------------------------------------------------------------- kernel 2: per-packet maximum and sum
+
+__global__ __launch_bounds__(64) void demod_packet_kernel(DemodLaunch a) {
+    __shared__ float buf[64];
+    const long long p = blockIdx.x;
+    const int lane = threadIdx.x;
+    const long long X0 = p * a.ps, X1 = min((p + 1) * a.ps, a.n);
+    const long long lo = pre_lower(a, X0), hi = pre_lower(a, X1);
+    float m = -INFINITY;
+    for (long long q = lo + lane; q < hi; q += 64) {
+        const float x = a.pre[q];
+        if (x > m) m = x;                                 // NaN never wins, as in the reference
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float o = __shfl_xor(m, off);
+        if (o > m) m = o;
+    }
+    float avg = 0.0f;
+    if (a.kind == kKindAm) {
+        float s = 0.0f;
+        for (long long base = lo; base < hi; base += 64) {
+            buf[lane] = base + lane < hi ? a.pre[base + lane] : 0.0f;
+            __syncthreads();
+            if (lane == 0) {
+                const int cnt = (int)min(64LL, hi - base);
+                for (int j = 0; j < cnt; j++) s = s + buf[j];
+            }
+            __syncthreads();
+        }
+        avg = s / (float)(int)(hi - lo);
+    }
+    if (lane == 0) {
+        a.pk_max[p] = m;
+        a.pk_avg[p] = avg;
+    }
+}
+
+// ---------------------------------------------------------------- kernel 3: state for the next call
+
+__global__ __launch_bounds__(kTile) void demod_state_kernel(DemodLaunch a) {
+    const int t = threadIdx.x;
+    if (t == 0) {
+        float lm = a.st[ST_LMAX];
+        if (a.agc) {
+            for (long long p = 0; p < a.K; p++) {
+                lm = lm * 0.95f;
+                const float m = a.pk_max[p];
+                if (m > lm) lm = m;
+                a.pk_gain[p] = 0.75f / lm;
+            }
+        }
+        a.nst[ST_LMAX] = lm;
+    }
+    if (t < kMaxUserTaps) {
+        float r = 0.0f, s = 0.0f;
+        if (t < a.Tu - 1) in_at(a, a.n - (a.Tu - 1) + t, r, s);
+        a.nst[ST_UF_RE + t] = r;
+        a.nst[ST_UF_IM + t] = s;
+    }
+    if (t < kMaxBandTaps) {
+        float r = a.st[ST_BP_RE + t], s = a.st[ST_BP_IM + t];
+        if (a.kind == kKindBand && t < a.Tb - 1) {
+            const long long f = a.F - (a.Tb - 1) + t;
+            if (f < 0) {
+                r = a.st[ST_BP_RE + a.Tb - 1 + f];
+                s = a.st[ST_BP_IM + a.Tb - 1 + f];
+            } else {
+                filt_at(a, f, r, s);
+            }
+        }
+        a.nst[ST_BP_RE + t] = r;
+        a.nst[ST_BP_IM + t] = s;
+    }
+    if (t == 0) {
+        float r = a.st[ST_CARRY], s = a.st[ST_CARRY + 1];
+        if (a.kind == kKindFm && a.F > 0) filt_at(a, a.F - 1, r, s);
+        a.nst[ST_CARRY] = r;
+        a.nst[ST_CARRY + 1] = s;
+    }
+    __syncthreads();                                      // the gains of this call are written
+    if (t < kMaxAudioTaps) {
+        float v = a.st[ST_A1 + t];
+        if (a.sink >= 1 && t < a.T1 - 1) v = v_at(a, a.npre - (a.T1 - 1) + t);
+        a.nst[ST_A1 + t] = v;
+        float y = a.st[ST_A2 + t];
+        if (a.sink == 2 && t < a.T2 - 1) y = y1_at(a, a.ny1 - (a.T2 - 1) + t);
+        a.nst[ST_A2 + t] = y;
+    }
+}
+
+// ---------------------------------------------------------------- kernel 4: gain, volume, audio FIRs
+
+constexpr int kY1Max = (kTile - 1) * kA2Dec + kMaxAudioTaps;
+constexpr int kVMax = (kY1Max - 1) * kA1Dec + kMaxAudioTaps;
+
+__global__ __launch_bounds__(kTile) void demod_audio_kernel(DemodLaunch a) {
+    __shared__ float vb[kVMax], yb[kY1Max], t1[kMaxAudioTaps], t2[kMaxAudioTaps];
+    const int tid = threadIdx.x;
+    const long long o0 = (long long)blockIdx.x * kTile;
+    const int nloc = (int)min((long long)kTile, a.n_audio - o0);
+    if (a.sink == 0) {
+        if (tid < nloc) a.out[o0 + tid] = v_at(a, o0 + tid);
+        return;
+    }
+    if (tid < a.T1) t1[tid] = a.taps[TP_A1 + tid];
+    if (tid < a.T2) t2[tid] = a.taps[TP_A2 + tid];
+    if (a.sink == 1) {
+        const long long clo = c1_of(a, o0) - (a.T1 - 1), chi = c1_of(a, o0 + nloc - 1);
+        const int nv = (int)(chi - clo + 1);
+        for (int i = tid; i < nv; i += kTile) vb[i] = v_at(a, clo + i);
+        __syncthreads();
+        if (tid < nloc) {
+            const float *x = vb + (int)(c1_of(a, o0 + tid) - clo);
+            float s = 0.0f;
+            for (int k = 0; k < a.T1; k++) s = s + t1[k] * x[-k];
+            a.out[o0 + tid] = s;
+        }
+        return;
+    }
+    // audioFilter2 output o has its newest input at audioFilter1 output r(o) of this call
+    const long long r_first = (a.a2_out0 + o0) * kA2Dec + (kA2Dec - 1) - a.a2_in0;
+    const long long rlo = r_first - (a.T2 - 1), rhi = r_first + (long long)(nloc - 1) * kA2Dec;
+    const long long rclo = rlo < 0 ? 0 : rlo;
+    const int nhist = (int)(rclo - rlo), nr = (int)(rhi - rlo + 1);
+    const long long vlo = c1_of(a, rclo) - (a.T1 - 1), vhi = c1_of(a, rhi);
+    const int nv = (int)(vhi - vlo + 1);
+    for (int i = tid; i < nv; i += kTile) vb[i] = v_at(a, vlo + i);
+    for (int j = tid; j < nhist; j += kTile) yb[j] = a.st[ST_A2 + a.T2 - 1 + rlo + j];
+    __syncthreads();
+    for (int j = nhist + tid; j < nr; j += kTile) {
+        const float *x = vb + (int)(c1_of(a, rlo + j) - vlo);
+        float s = 0.0f;
+        for (int k = 0; k < a.T1; k++) s = s + t1[k] * x[-k];
+        yb[j] = s;
+    }
+    __syncthreads();
+    if (tid < nloc) {
+        const float *y = yb + (a.T2 - 1) + tid * kA2Dec;
+        float s = 0.0f;
+        for (int k = 0; k < a.T2; k++) s = s + t2[k] * y[-k];
+        a.out[o0 + tid] = s;
+    }
+}
+
+// ---------------------------------------------------------------- host design
+
+// Java/Kotlin (int) of a double: truncation, saturation, NaN -> 0.
+int32_t jtoint(double x) {
+    if (x != x) return 0;
+    if (x >= 2147483647.0) return INT32_MAX;
+    if (x <= -2147483648.0) return INT32_MIN;
+    return (int32_t)x;
+}
+
+// Blackman window as both filter classes compute it (WindowFunctions.kt:44-49,
+// ComplexFirFilter.java:270-278): cosines in double, cast, float arithmetic.
+float blackman(int n, int N) {
+    const float c1 = (float)std::cos(2.0 * M_PI * n / (N - 1));
+    const float c2 = (float)std::cos(4.0 * M_PI * n / (N - 1));
+    return 0.42f - 0.5f * c1 + 0.08f * c2;
+}
+
+// The windowed-sinc low-pass prototype both designs share (FirFilter.kt:160-195,
+// ComplexFirFilter.java:224-246), normalised to `gain` at zero frequency.
+void low_pass_prototype(float gain, float fs, float fc, int ntaps, std::vector<float> &taps) {
+    taps.assign(ntaps, 0.0f);
+    const float pi = (float)M_PI;
+    const int M = (ntaps - 1) / 2;
+    const float fwT0 = 2 * pi * fc / fs;
+    for (int n = -M; n <= M; n++) {
+        const float w = blackman(n + M, ntaps);
+        if (n == 0) taps[n + M] = fwT0 / pi * w;
+        else taps[n + M] = (float)std::sin((double)((float)n * fwT0)) / ((float)n * pi) * w;
+    }
+    float fmx = taps[M];
+    for (int n = 1; n <= M; n++) fmx += 2 * taps[n + M];
+    const float g = gain / fmx;
+    for (float &t : taps) t *= g;
+}
+
+// FirFilter.createLowPassTaps (FirFilter.kt:182-195, Blackman, no tap limit).
+bool design_low_pass(float gain, float fs, float fc, float tw, float att, std::vector<float> &taps) {
+    if (fs <= 0.0f || fc <= 0.0f || fc > fs / 2 || tw <= 0.0f) return false;
+    int ntaps = jtoint((double)(att * fs) / (22.0 * (double)tw));
+    if ((ntaps & 1) == 0) ntaps++;
+    if (ntaps <= 0 || ntaps > (1 << 20)) return false;
+    low_pass_prototype(gain, fs, fc, ntaps, taps);
+    return true;
+}
+
+// ComplexFirFilter.createBandPass (ComplexFirFilter.java:186-262).
+bool design_band_pass(float gain, float fs, float lo, float hi, float tw, float att, std::vector<float> &re,
+                      std::vector<float> &im) {
+    if (!(fs > 0.0f)) return false;
+    if ((double)lo < (double)fs * -0.5 || (double)hi > (double)fs * 0.5) return false;
+    if (!(lo < hi)) return false;
+    if (!(tw > 0.0f)) return false;
+    int ntaps = jtoint((double)(att * fs) / (22.0 * (double)tw));
+    if ((ntaps & 1) == 0) ntaps++;
+    if (ntaps <= 0 || ntaps > (1 << 20)) return false;
+    std::vector<float> lp;
+    low_pass_prototype(gain, fs, (hi - lo) / 2.0f, ntaps, lp);
+    re.assign(ntaps, 0.0f);
+    im.assign(ntaps, 0.0f);
+    const float freq = (float)M_PI * (hi + lo) / fs;
+    float phase = -freq * (float)(ntaps / 2);
+    for (int i = 0; i < ntaps; i++) {
+        re[i] = lp[i] * (float)std::cos((double)phase);
+        im[i] = lp[i] * (float)std::sin((double)phase);
+        phase += freq;
+    }
+    return true;
+}
+
+struct ModeInfo {
+    int32_t rate, min_w, max_w, def_w;
+};
+
+// DemodulationMode's widths and Demodulator.kt:52-61.
+const ModeInfo kModes[7] = {
+    {2 * kAudioRate, 0, 50000, 0},             // OFF (the rate is a dummy)
+    {2 * kAudioRate, 3000, 15000, 8000},       // AM
+    {2 * kAudioRate, 3000, 15000, 10000},      // NFM
+    {8 * kAudioRate, 30000, 150000, 100000},   // WFM
+    {2 * kAudioRate, 1500, 5000, 2800},        // LSB
+    {2 * kAudioRate, 1500, 5000, 2800},        // USB
+    {1 * kAudioRate, 150, 800, 300},           // CW
+};
+constexpr int kCwOffset = 750;                 // Demodulator.kt:67
+
+bool mode_ok(int mode) { return mode >= RFA_DEMOD_OFF && mode <= RFA_DEMOD_CW; }
+
+long long fir_off(int D) { return D >= 2 ? D - 1 : 1; }
+
+// outputs of a FirFilter once in_total inputs went in since it was built
+long long fir_outputs(int D, long long in_total) {
+    const long long lim = in_total - fir_off(D);
+    return lim > 0 ? (lim + D - 1) / D : 0;
+}
+
+}  // namespace
+
+struct rfa_demod {
+    int device = 0;
+    int mode = RFA_DEMOD_OFF;
+    int32_t width = 0;
+    float volume = 1.0f;
+    bool sink_enabled = true;
+    hipStream_t stream = nullptr, own_stream = nullptr;
+    std::string err;
+    // userFilter (Demodulator.kt:73,215-240)
+    bool uf_valid = false;
+    std::vector<float> uf_taps;
+    float uf_cutoff = 0.0f;
+    long long uf_in = 0;
+    // bandPassFilter, shared by SSB and CW (Demodulator.kt:87)
+    bool bp_valid = false;
+    std::vector<float> bp_re, bp_im;
+    float bp_lo = 0.0f, bp_hi = 0.0f;
+    int bp_dec = 1;
+    long long bp_in = 0, bp_out = 0;
+    // AudioSink.audioFilter1 / audioFilter2
+    std::vector<float> a1_taps, a2_taps;
+    long long a1_in = 0, a1_out = 0, a2_in = 0, a2_out = 0;
+    // device
+    float *d_state[2] = {nullptr, nullptr};
+    int cur = 0;
+    float *d_taps = nullptr;
+    float *d_pre = nullptr;
+    size_t pre_cap = 0;
+    float *d_pk = nullptr;         // [max K | avg K | gain K]
+    size_t pk_cap = 0;
+    float *d_in = nullptr, *d_out = nullptr;   // staging of the _host entry
+    size_t d_in_cap = 0, d_out_cap = 0;
+};
+
+namespace {
+
+int mfail(rfa_demod *d, int code, const std::string &msg) {
+    if (d) d->err = msg;
+    return code;
+}
+
+#define MHIP(d, expr)                                                                  \
+    do {                                                                               \
+        hipError_t _e = (expr);                                                        \
+        if (_e != hipSuccess) return mfail((d), RFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// Demodulator.kt:217: userFilter == null || cutOffFrequency.toInt() != channelWidth
+bool uf_stale(const rfa_demod *d) { return !d->uf_valid || jtoint((double)d->uf_cutoff) != d->width; }
+
+// Demodulator.kt:321-322 (SSB) and :370 (CW), literally
+bool bp_stale(const rfa_demod *d) {
+    if (!d->bp_valid) return true;
+    if (d->mode == RFA_DEMOD_USB) return jtoint((double)d->bp_hi) != d->width;
+    if (d->mode == RFA_DEMOD_LSB) return jtoint((double)d->bp_lo) != -d->width;
+    return jtoint((double)d->bp_hi) != kCwOffset + d->width / 2;
+}
+
+bool is_band(int mode) { return mode == RFA_DEMOD_LSB || mode == RFA_DEMOD_USB || mode == RFA_DEMOD_CW; }
+
+// What one call does, from the host's counters alone.
+struct Plan {
+    bool uf_fresh = false, bp_fresh = false;
+    int kind = kKindAm, Db = 1, sink = 0;
+    long long K = 1, ps = 1, skip = 0, F = 0;
+    long long bp_in0 = 0, bp_out0 = 0, npre = 0, ny1 = 0, n_audio = 0;
+};
+
+void make_plan(const rfa_demod *d, long long n, long long packet, Plan &p) {
+    p.ps = packet > 0 ? packet : std::max(1LL, n);
+    p.K = std::max(1LL, (n + p.ps - 1) / p.ps);
+    p.uf_fresh = uf_stale(d);
+    const long long uf_in = p.uf_fresh ? 0 : d->uf_in;
+    p.skip = (uf_in == 0 && n > 0) ? 1 : 0;
+    p.F = n - p.skip;
+    int rate = kModes[d->mode].rate;
+    if (is_band(d->mode)) {
+        p.kind = kKindBand;
+        p.bp_fresh = bp_stale(d);
+        p.Db = p.bp_fresh ? (d->mode == RFA_DEMOD_CW ? 1 : 2) : d->bp_dec;
+        p.bp_in0 = p.bp_fresh ? 0 : d->bp_in;
+        p.bp_out0 = p.bp_fresh ? 0 : d->bp_out;
+        p.npre = fir_outputs(p.Db, p.bp_in0 + p.F) - p.bp_out0;
+        rate /= p.Db;
+    } else {
+        p.kind = d->mode == RFA_DEMOD_AM ? kKindAm : kKindFm;
+        p.npre = p.F;
+    }
+    // AudioSink.java:182,217,229: by the packet's sample rate
+    const int ratio = rate / kAudioRate;
+    p.sink = !d->sink_enabled ? 0 : (ratio == 8 ? 2 : (ratio == 2 ? 1 : 0));
+    p.n_audio = p.npre;
+    if (p.sink >= 1) p.ny1 = p.n_audio = fir_outputs(kA1Dec, d->a1_in + p.npre) - d->a1_out;
+    if (p.sink == 2) p.n_audio = fir_outputs(kA2Dec, d->a2_in + p.ny1) - d->a2_out;
+}
+
+int upload_taps(rfa_demod *d, int at, const std::vector<float> &t) {
+    MHIP(d, hipMemcpyAsync(d->d_taps + at, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    MHIP(d, hipStreamSynchronize(d->stream));
+    return RFA_OK;
+}
+
+int rebuild_user_filter(rfa_demod *d) {
+    const float rate = (float)kModes[d->mode].rate;
+    std::vector<float> t;
+    // createLowPass(1, 1f, rate, width, rate * 0.10f, 60) (Demodulator.kt:219-226)
+    if (!design_low_pass(1.0f, rate, (float)d->width, rate * 0.10f, 60.0f, t))
+        return mfail(d, RFA_ERR_INVALID, "user filter design rejected the width (createLowPass returns null)");
+    if (t.size() > (size_t)kMaxUserTaps) return mfail(d, RFA_ERR_UNSUPPORTED, "user filter longer than the kernel's limit");
+    MHIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_UF_RE, 0, 2 * kMaxUserTaps * sizeof(float), d->stream));
+    const int rc = upload_taps(d, TP_UF, t);
+    if (rc != RFA_OK) return rc;
+    d->uf_taps = std::move(t);
+    d->uf_cutoff = (float)d->width;
+    d->uf_in = 0;
+    d->uf_valid = true;
+    return RFA_OK;
+}
+
+int rebuild_band_pass(rfa_demod *d) {
+    const float rate = (float)kModes[d->mode].rate, w = (float)d->width;
+    float lo, hi;
+    int dec = 2;
+    if (d->mode == RFA_DEMOD_USB) lo = 200.0f, hi = w;                 // Demodulator.kt:325-333
+    else if (d->mode == RFA_DEMOD_LSB) lo = -w, hi = -200.0f;
+    else lo = (float)kCwOffset - w / 2.0f, hi = (float)kCwOffset + w / 2.0f, dec = 1;   // :372-380
+    std::vector<float> re, im;
+    if (!design_band_pass(1.0f, rate, lo, hi, rate * 0.01f, 40.0f, re, im))
+        return mfail(d, RFA_ERR_INVALID, "band-pass design rejected the width (createBandPass returns null)");
+    if (re.size() > (size_t)kMaxBandTaps) return mfail(d, RFA_ERR_UNSUPPORTED, "band-pass filter longer than the kernel's limit");
+    MHIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_BP_RE, 0, 2 * kMaxBandTaps * sizeof(float), d->stream));
+    int rc = upload_taps(d, TP_BPR, re);
+    if (rc == RFA_OK) rc = upload_taps(d, TP_BPI, im);
+    if (rc != RFA_OK) return rc;
+    d->bp_re = std::move(re);
+    d->bp_im = std::move(im);
+    d->bp_lo = lo;
+    d->bp_hi = hi;
+    d->bp_dec = dec;
+    d->bp_in = d->bp_out = 0;
+    d->bp_valid = true;
+    return RFA_OK;
+}
+
+// A freshly created Demodulator + AudioSink: no user or band-pass filter, zero
+// carry-over and lastMax, audio filters with empty delay lines.
+int fresh_state(rfa_demod *d) {
+    MHIP(d, hipMemsetAsync(d->d_state[d->cur], 0, ST_SIZE * sizeof(float), d->stream));
+    d->uf_valid = d->bp_valid = false;
+    d->uf_in = d->bp_in = d->bp_out = 0;
+    d->a1_in = d->a1_out = d->a2_in = d->a2_out = 0;
+    return RFA_OK;
+}
+
+int grow(rfa_demod *d, float *&p, size_t &cap, size_t want, const char *what) {
+    if (want <= cap) return RFA_OK;
+    MHIP(d, hipStreamSynchronize(d->stream));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    want = std::max(want, (size_t)4096);
+    if (hipMalloc(&p, want * sizeof(float)) != hipSuccess) return mfail(d, RFA_ERR_NOMEM, std::string("hipMalloc ") + what);
+    cap = want;
+    return RFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rfa_demod_mode_info(int mode, int32_t *quadrature_rate, int32_t *min_width, int32_t *max_width,
+                        int32_t *default_width) {
+    if (!mode_ok(mode)) return RFA_ERR_INVALID;
+    const ModeInfo &m = kModes[mode];
+    if (quadrature_rate) *quadrature_rate = m.rate;
+    if (min_width) *min_width = m.min_w;
+    if (max_width) *max_width = m.max_w;
+    if (default_width) *default_width = m.def_w;
+    return RFA_OK;
+}
+
+int rfa_bandpass_taps(float gain, float fs, float lo, float hi, float transition, float attenuation, float *re,
+                      float *im, size_t capacity, int32_t *num_taps) {
+    if (!num_taps) return RFA_ERR_INVALID;
+    *num_taps = 0;
+    std::vector<float> r, i;
+    if (!design_band_pass(gain, fs, lo, hi, transition, attenuation, r, i)) return RFA_ERR_INVALID;
+    *num_taps = (int32_t)r.size();
+    if (re || im) {
+        if (capacity < r.size()) return RFA_ERR_SIZE;
+        if (re) std::memcpy(re, r.data(), r.size() * sizeof(float));
+        if (im) std::memcpy(im, i.data(), i.size() * sizeof(float));
+    }
+    return RFA_OK;
+}
+
+int rfa_demod_create(int device, int mode, rfa_demod **out) {
+    if (!out) return RFA_ERR_INVALID;
+    *out = nullptr;
+    if (!mode_ok(mode)) return RFA_ERR_INVALID;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
+    if (device < 0 || device >= count) return RFA_ERR_INVALID;
+    rfa_demod *d = new (std::nothrow) rfa_demod();
+    if (!d) return RFA_ERR_NOMEM;
+    d->device = device;
+    d->mode = mode;
+    d->width = kModes[mode].def_w;
+    int rc = RFA_OK;
+    std::vector<float> t1, t2;
+    // AudioSink.java:94-96: createLowPass(decimation 2 / 4, gain 1, rate 1, cut-off, transition, 30 dB)
+    if (!design_low_pass(1.0f, 1.0f, 0.1f, 0.15f, 30.0f, t1) || !design_low_pass(1.0f, 1.0f, 0.1f, 0.1f, 30.0f, t2) ||
+        t1.size() > (size_t)kMaxAudioTaps || t2.size() > (size_t)kMaxAudioTaps)
+        rc = RFA_ERR_INVALID;
+    if (rc == RFA_OK && (hipSetDevice(device) != hipSuccess ||
+                         hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess))
+        rc = RFA_ERR_HIP;
+    if (rc == RFA_OK) {
+        if (hipMalloc(&d->d_state[0], ST_SIZE * sizeof(float)) != hipSuccess ||
+            hipMalloc(&d->d_state[1], ST_SIZE * sizeof(float)) != hipSuccess ||
+            hipMalloc(&d->d_taps, TP_SIZE * sizeof(float)) != hipSuccess)
+            rc = RFA_ERR_NOMEM;
+    }
+    if (rc == RFA_OK && (hipMemsetAsync(d->d_taps, 0, TP_SIZE * sizeof(float), d->stream) != hipSuccess ||
+                         hipMemsetAsync(d->d_state[1], 0, ST_SIZE * sizeof(float), d->stream) != hipSuccess))
+        rc = RFA_ERR_HIP;
+    if (rc == RFA_OK) rc = fresh_state(d);
+    if (rc == RFA_OK) rc = upload_taps(d, TP_A1, t1);
+    if (rc == RFA_OK) rc = upload_taps(d, TP_A2, t2);
+    if (rc != RFA_OK) {
+        rfa_demod_destroy(d);
+        return rc;
+    }
+    d->a1_taps = std::move(t1);
+    d->a2_taps = std::move(t2);
+    *out = d;
+    return RFA_OK;
+}
+
+int rfa_demod_destroy(rfa_demod *d) {
+    if (!d) return RFA_ERR_INVALID;
+    (void)hipSetDevice(d->device);
+    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    for (float *p : {d->d_state[0], d->d_state[1], d->d_taps, d->d_pre, d->d_pk, d->d_in, d->d_out})
+        if (p) (void)hipFree(p);
+    hipStream_t own = d->own_stream ? d->own_stream : d->stream;
+    if (own) (void)hipStreamDestroy(own);
+    delete d;
+    return RFA_OK;
+}
+
+const char *rfa_demod_last_error(const rfa_demod *d) { return d ? d->err.c_str() : "null handle"; }
+
+int rfa_demod_set_mode(rfa_demod *d, int mode) {
+    if (!d) return RFA_ERR_INVALID;
+    if (!mode_ok(mode)) return mfail(d, RFA_ERR_INVALID, "no such demodulation mode");
+    d->mode = mode;                       // Demodulator.kt:96-100
+    d->width = kModes[mode].def_w;
+    return RFA_OK;
+}
+
+int rfa_demod_get_mode(const rfa_demod *d, int32_t *mode) {
+    if (!d || !mode) return RFA_ERR_INVALID;
+    *mode = d->mode;
+    return RFA_OK;
+}
+
+int rfa_demod_set_channel_width(rfa_demod *d, int32_t w) {
+    if (!d) return RFA_ERR_INVALID;
+    const ModeInfo &m = kModes[d->mode];  // Demodulator.kt:75
+    d->width = std::min(std::max(w, m.min_w), m.max_w);
+    return RFA_OK;
+}
+
+int rfa_demod_get_channel_width(const rfa_demod *d, int32_t *w) {
+    if (!d || !w) return RFA_ERR_INVALID;
+    *w = d->width;
+    return RFA_OK;
+}
+
+int rfa_demod_set_volume(rfa_demod *d, float v) {
+    if (!d) return RFA_ERR_INVALID;
+    d->volume = v;
+    return RFA_OK;
+}
+
+int rfa_demod_set_audio_sink(rfa_demod *d, int enable) {
+    if (!d) return RFA_ERR_INVALID;
+    d->sink_enabled = enable != 0;
+    return RFA_OK;
+}
+
+int rfa_demod_max_outputs(const rfa_demod *d, size_t n_samples, size_t *n) {
+    if (!d || !n) return RFA_ERR_INVALID;
+    *n = 0;
+    if (d->mode == RFA_DEMOD_OFF) return RFA_OK;
+    if (n_samples > (size_t)1 << 36) return RFA_ERR_INVALID;
+    Plan p;
+    make_plan(d, (long long)n_samples, 0, p);
+    *n = (size_t)p.n_audio;
+    return RFA_OK;
+}
+
+int rfa_demod_process(rfa_demod *d, const float *re, const float *im, size_t n_samples, size_t packet_samples,
+                      float *audio, size_t capacity, size_t *n_audio) {
+    if (!d || !n_audio) return RFA_ERR_INVALID;
+    *n_audio = 0;
+    if (d->mode == RFA_DEMOD_OFF) return RFA_OK;          // Demodulator.kt:174: no output, nothing moves
+    if (n_samples > (size_t)1 << 36 || packet_samples > (size_t)1 << 36)
+        return mfail(d, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return mfail(d, RFA_ERR_INVALID, "null input");
+    Plan p;
+    make_plan(d, (long long)n_samples, (long long)packet_samples, p);
+    if ((size_t)p.n_audio > capacity) return mfail(d, RFA_ERR_SIZE, "audio capacity too small");
+    if (p.n_audio > 0 && !audio) return mfail(d, RFA_ERR_INVALID, "null output");
+    if (p.K > (long long)INT32_MAX || (p.npre + kTile - 1) / kTile > (long long)INT32_MAX)
+        return mfail(d, RFA_ERR_INVALID, "call too large for one grid");
+    MHIP(d, hipSetDevice(d->device));
+    int rc = grow(d, d->d_pre, d->pre_cap, (size_t)p.npre, "scratch");
+    if (rc == RFA_OK) rc = grow(d, d->d_pk, d->pk_cap, 3 * (size_t)p.K, "packet scratch");
+    if (rc == RFA_OK && p.uf_fresh) rc = rebuild_user_filter(d);
+    if (rc == RFA_OK && p.bp_fresh) rc = rebuild_band_pass(d);
+    if (rc != RFA_OK) return rc;
+
+    DemodLaunch a{};
+    a.re = re;
+    a.im = im;
+    a.n = (long long)n_samples;
+    a.ps = p.ps;
+    a.K = p.K;
+    a.st = d->d_state[d->cur];
+    a.nst = d->d_state[d->cur ^ 1];
+    a.taps = d->d_taps;
+    a.kind = p.kind;
+    a.Tu = (int)d->uf_taps.size();
+    a.Tb = p.kind == kKindBand ? (int)d->bp_re.size() : 1;
+    a.T1 = (int)d->a1_taps.size();
+    a.T2 = (int)d->a2_taps.size();
+    a.Db = p.Db;
+    a.offb = p.kind == kKindBand ? (int)fir_off(p.Db) : 0;
+    a.skip = (int)p.skip;
+    a.F = p.F;
+    a.bp_in0 = p.bp_in0;
+    a.bp_out0 = p.bp_out0;
+    a.npre = p.npre;
+    if (p.kind == kKindFm) {
+        // quadratureRate / (2 * PI * maxDeviation).toFloat() (Demodulator.kt:176-177,257)
+        const float dev = (float)d->width * (d->mode == RFA_DEMOD_NFM ? 0.75f : 0.85f);
+        a.qgain = (float)kModes[d->mode].rate / (float)(2 * M_PI * (double)dev);
+    }
+    a.volume = d->volume;
+    a.agc = p.kind != kKindFm;
+    a.sink = p.sink;
+    a.a1_in0 = d->a1_in;
+    a.a1_out0 = d->a1_out;
+    a.ny1 = p.ny1;
+    a.a2_in0 = d->a2_in;
+    a.a2_out0 = d->a2_out;
+    a.n_audio = p.n_audio;
+    a.pre = d->d_pre;
+    a.pk_max = d->d_pk;
+    a.pk_avg = d->d_pk + p.K;
+    a.pk_gain = d->d_pk + 2 * p.K;
+    a.out = audio;
+
+    if (p.npre > 0) {
+        hipLaunchKernelGGL(demod_stage1_kernel, dim3((unsigned)((p.npre + kTile - 1) / kTile)), dim3(kTile), 0,
+                           d->stream, a);
+        MHIP(d, hipGetLastError());
+    }
+    if (a.agc) {
+        hipLaunchKernelGGL(demod_packet_kernel, dim3((unsigned)p.K), dim3(64), 0, d->stream, a);
+        MHIP(d, hipGetLastError());
+    }
+    hipLaunchKernelGGL(demod_state_kernel, dim3(1), dim3(kTile), 0, d->stream, a);
+    MHIP(d, hipGetLastError());
+    if (p.n_audio > 0) {
+        hipLaunchKernelGGL(demod_audio_kernel, dim3((unsigned)((p.n_audio + kTile - 1) / kTile)), dim3(kTile), 0,
+                           d->stream, a);
+        MHIP(d, hipGetLastError());
+    }
+    d->cur ^= 1;
+    d->uf_in += (long long)n_samples;
+    if (p.kind == kKindBand) {
+        d->bp_in += p.F;
+        d->bp_out += p.npre;
+    }
+    if (p.sink >= 1) {
+        d->a1_in += p.npre;
+        d->a1_out += p.ny1;
+    }
+    if (p.sink == 2) {
+        d->a2_in += p.ny1;
+        d->a2_out += p.n_audio;
+    }
+    *n_audio = (size_t)p.n_audio;
+    return RFA_OK;
+}
+
+int rfa_demod_process_host(rfa_demod *d, const float *re, const float *im, size_t n_samples, size_t packet_samples,
+                           float *audio, size_t capacity, size_t *n_audio) {
+    if (!d || !n_audio) return RFA_ERR_INVALID;
+    *n_audio = 0;
+    if (d->mode == RFA_DEMOD_OFF) return RFA_OK;
+    if (n_samples > (size_t)1 << 36) return mfail(d, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return mfail(d, RFA_ERR_INVALID, "null input");
+    MHIP(d, hipSetDevice(d->device));
+    Plan p;
+    make_plan(d, (long long)n_samples, (long long)packet_samples, p);
+    if ((size_t)p.n_audio > capacity) return mfail(d, RFA_ERR_SIZE, "audio capacity too small");
+    int rc = grow(d, d->d_in, d->d_in_cap, 2 * n_samples, "input staging");
+    if (rc == RFA_OK) rc = grow(d, d->d_out, d->d_out_cap, (size_t)p.n_audio, "output staging");
+    if (rc != RFA_OK) return rc;
+    if (n_samples) {
+        MHIP(d, hipMemcpyAsync(d->d_in, re, n_samples * sizeof(float), hipMemcpyHostToDevice, d->stream));
+        MHIP(d, hipMemcpyAsync(d->d_in + n_samples, im, n_samples * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    }
+    size_t got = 0;
+    rc = rfa_demod_process(d, d->d_in, d->d_in + n_samples, n_samples, packet_samples, d->d_out, d->d_out_cap, &got);
+    if (rc != RFA_OK) return rc;
+    if (got) MHIP(d, hipMemcpyAsync(audio, d->d_out, got * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+    MHIP(d, hipStreamSynchronize(d->stream));
+    *n_audio = got;
+    return RFA_OK;
+}
+
+int rfa_demod_get_taps(const rfa_demod *d, int which, float *re, float *im, size_t capacity, int32_t *num_taps,
+                       int32_t *decimation) {
+    if (!d) return RFA_ERR_INVALID;
+    static const std::vector<float> none;
+    const std::vector<float> *r = &none, *i = nullptr;
+    int dec = 1;
+    switch (which) {
+    case RFA_DEMOD_TAPS_USER:
+        if (d->uf_valid) r = &d->uf_taps;
+        break;
+    case RFA_DEMOD_TAPS_BANDPASS:
+        if (d->bp_valid) r = &d->bp_re, i = &d->bp_im, dec = d->bp_dec;
+        break;
+    case RFA_DEMOD_TAPS_AUDIO1: r = &d->a1_taps, dec = kA1Dec; break;
+    case RFA_DEMOD_TAPS_AUDIO2: r = &d->a2_taps, dec = kA2Dec; break;
+    default: return RFA_ERR_INVALID;
+    }
+    if (num_taps) *num_taps = (int32_t)r->size();
+    if (decimation) *decimation = dec;
+    if (re || im) {
+        if (capacity < r->size()) return RFA_ERR_SIZE;
+        if (re) std::memcpy(re, r->data(), r->size() * sizeof(float));
+        if (im) {
+            if (i) std::memcpy(im, i->data(), i->size() * sizeof(float));
+            else std::memset(im, 0, r->size() * sizeof(float));
+        }
+    }
+    return RFA_OK;
+}
+
+int rfa_demod_get_state(rfa_demod *d, float *last_max, float *carry_re, float *carry_im) {
+    if (!d) return RFA_ERR_INVALID;
+    MHIP(d, hipSetDevice(d->device));
+    float s[3] = {0.0f, 0.0f, 0.0f};
+    MHIP(d, hipMemcpyAsync(s, d->d_state[d->cur] + ST_CARRY, sizeof s, hipMemcpyDeviceToHost, d->stream));
+    MHIP(d, hipStreamSynchronize(d->stream));
+    if (carry_re) *carry_re = s[0];
+    if (carry_im) *carry_im = s[1];
+    if (last_max) *last_max = s[2];
+    return RFA_OK;
+}
+
+int rfa_demod_reset(rfa_demod *d) {
+    if (!d) return RFA_ERR_INVALID;
+    MHIP(d, hipSetDevice(d->device));
+    return fresh_state(d);
+}
+
+int rfa_demod_set_stream(rfa_demod *d, void *stream) {
+    if (!d) return RFA_ERR_INVALID;
+    // the carried state is ordered on the handle's stream: drain it first
+    MHIP(d, hipSetDevice(d->device));
+    MHIP(d, hipStreamSynchronize(d->stream));
+    if (d->own_stream == nullptr) d->own_stream = d->stream;
+    d->stream = stream ? (hipStream_t)stream : d->own_stream;
+    return RFA_OK;
+}
+
+int rfa_demod_get_stream(const rfa_demod *d, void **stream) {
+    if (!d || !stream) return RFA_ERR_INVALID;
+    *stream = (void *)d->stream;
+    return RFA_OK;
+}
+
+int rfa_demod_synchronize(rfa_demod *d) {
+    if (!d) return RFA_ERR_INVALID;
+    MHIP(d, hipSetDevice(d->device));
+    MHIP(d, hipStreamSynchronize(d->stream));
+    return RFA_OK;
+}
+
+}  // extern "C"

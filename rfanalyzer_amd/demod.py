@@ -17,6 +17,11 @@ the C-ABI ``rfa_ddc_*`` (include/rfa.h).  Filter and mixer state carry over betw
 calls exactly as in the reference, so feeding packets one by one or a whole buffer
 at once gives the same samples.  There is no CPU fallback: without librfa.so or a
 HIP device every call raises.
+
+``Demodulator`` is what follows in the app -- analyzer/Demodulator.kt:151-403 with the
+AudioSink's decimators (analyzer/AudioSink.java:94-97,215-237): quadrature-rate samples
+to 48 kHz audio through ``rfa_demod_*`` (``rfanalyzer_amd/csrc/demod.hip``) -- and
+``Receiver`` chains a ``FrontEnd`` into it, raw IQ bytes to audio on one stream.
 """
 from __future__ import annotations
 
@@ -227,3 +232,313 @@ class FirFilter(FrontEnd):
         iq = np.empty(2 * re.size, np.float32)
         iq[0::2], iq[1::2] = re, im
         return self.process(iq)
+
+
+# ---------------------------------------------------------------- demodulator proper
+
+MODES = {"off": 0, "am": 1, "nfm": 2, "wfm": 3, "lsb": 4, "usb": 5, "cw": 6}
+TAPS = {"user": 0, "bandpass": 1, "audio1": 2, "audio2": 3}
+AUDIO_RATE = 48000
+
+
+def _mode_id(mode) -> int:
+    if isinstance(mode, str):
+        if mode.lower() not in MODES:
+            raise ValueError(f"mode must be one of {sorted(MODES)}")
+        return MODES[mode.lower()]
+    return int(mode)
+
+
+def mode_info(mode):
+    """(quadrature rate, min, max, default channel width) of a DemodulationMode
+    (analyzer/Demodulator.kt:52-61).  Host-only."""
+    v = [ctypes.c_int32(0) for _ in range(4)]
+    _lib.check(_lib.lib().rfa_demod_mode_info(_mode_id(mode), *[ctypes.byref(x) for x in v]), "rfa_demod_mode_info")
+    return tuple(x.value for x in v)
+
+
+def create_band_pass_taps(gain: float, sample_rate: float, low_cutoff: float, high_cutoff: float,
+                          transition_width: float, attenuation_db: float):
+    """ComplexFirFilter.createBandPass's taps (dsp/ComplexFirFilter.java:186-262) as (re, im);
+    None where the reference returns null.  Host-only."""
+    L = _lib.lib()
+    n = ctypes.c_int32(0)
+    args = (gain, sample_rate, low_cutoff, high_cutoff, transition_width, attenuation_db)
+    st = L.rfa_bandpass_taps(*args, None, None, 0, ctypes.byref(n))
+    if st == _lib.RFA_ERR_INVALID:
+        return None
+    _lib.check(st, "rfa_bandpass_taps")
+    re = np.empty(n.value, np.float32)
+    im = np.empty(n.value, np.float32)
+    _lib.check(L.rfa_bandpass_taps(*args, re.ctypes.data_as(_lib._fp), im.ctypes.data_as(_lib._fp), re.size,
+                                   ctypes.byref(n)), "rfa_bandpass_taps")
+    return re, im
+
+
+class Demodulator:
+    """analyzer/Demodulator.kt with its AudioSink on ``device``: quadrature-rate planar IQ
+    in, 48 kHz float audio out (``rfanalyzer_amd/csrc/demod.hip`` through ``rfa_demod_*``).
+
+    ``demodulationMode``, ``channelWidth`` and ``audioVolumeLevel`` behave as the Kotlin
+    properties: setting the mode sets the width to the mode's default, the width is coerced
+    into the mode's range, and every filter, AGC and carry-over state survives both.  A call
+    may carry several packets (``packet_samples``); the result equals the reference run
+    packet by packet.  ``audio_sink=False`` returns the demodulator's own audio buffer at the
+    packet rate instead of the AudioSink's 48 kHz stream."""
+
+    def __init__(self, mode="off", device: int = 0, audio_sink: bool = True):
+        self._h = None
+        self._stream = None
+        h = _lib._h()
+        _lib.check(_lib.lib().rfa_demod_create(device, _mode_id(mode), ctypes.byref(h)), "rfa_demod_create")
+        self._h = h
+        if not audio_sink:
+            self.audio_sink = False
+
+    # -- lifetime
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.lib().rfa_demod_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def _check(self, status: int, where: str) -> None:
+        if status != _lib.RFA_OK:
+            detail = (_lib.lib().rfa_demod_last_error(self._h) or b"").decode()
+            raise _lib.RfaError(status, where, detail)
+
+    # -- the Kotlin properties
+    @property
+    def demodulationMode(self) -> int:  # noqa: N802
+        m = ctypes.c_int32(0)
+        self._check(_lib.lib().rfa_demod_get_mode(self._h, ctypes.byref(m)), "rfa_demod_get_mode")
+        return m.value
+
+    @demodulationMode.setter
+    def demodulationMode(self, mode) -> None:  # noqa: N802
+        self._check(_lib.lib().rfa_demod_set_mode(self._h, _mode_id(mode)), "rfa_demod_set_mode")
+
+    @property
+    def channelWidth(self) -> int:  # noqa: N802
+        w = ctypes.c_int32(0)
+        self._check(_lib.lib().rfa_demod_get_channel_width(self._h, ctypes.byref(w)), "rfa_demod_get_channel_width")
+        return w.value
+
+    @channelWidth.setter
+    def channelWidth(self, width: int) -> None:  # noqa: N802
+        self._check(_lib.lib().rfa_demod_set_channel_width(self._h, int(width)), "rfa_demod_set_channel_width")
+
+    @property
+    def audioVolumeLevel(self) -> float:  # noqa: N802
+        return getattr(self, "_volume", 1.0)
+
+    @audioVolumeLevel.setter
+    def audioVolumeLevel(self, v: float) -> None:  # noqa: N802
+        self._check(_lib.lib().rfa_demod_set_volume(self._h, float(v)), "rfa_demod_set_volume")
+        self._volume = float(np.float32(v))
+
+    @property
+    def audio_sink(self) -> bool:
+        return getattr(self, "_sink", True)
+
+    @audio_sink.setter
+    def audio_sink(self, enable: bool) -> None:
+        self._check(_lib.lib().rfa_demod_set_audio_sink(self._h, 1 if enable else 0), "rfa_demod_set_audio_sink")
+        self._sink = bool(enable)
+
+    @property
+    def quadrature_rate(self) -> int:
+        return mode_info(self.demodulationMode)[0]
+
+    # -- inspection
+    def taps(self, which: str):
+        """("user" | "bandpass" | "audio1" | "audio2") -> (re, im, decimation); empty before a
+        packet has built the user or band-pass filter."""
+        n, d = ctypes.c_int32(0), ctypes.c_int32(0)
+        L = _lib.lib()
+        self._check(L.rfa_demod_get_taps(self._h, TAPS[which], None, None, 0, ctypes.byref(n), ctypes.byref(d)),
+                    "rfa_demod_get_taps")
+        re = np.empty(n.value, np.float32)
+        im = np.empty(n.value, np.float32)
+        self._check(L.rfa_demod_get_taps(self._h, TAPS[which], re.ctypes.data_as(_lib._fp),
+                                         im.ctypes.data_as(_lib._fp), re.size, ctypes.byref(n), ctypes.byref(d)),
+                    "rfa_demod_get_taps")
+        return re, im, d.value
+
+    def state(self):
+        """(lastMax, carryOverSamplesRe, carryOverSamplesIm) as numpy float32; drains the stream."""
+        v = [ctypes.c_float(0) for _ in range(3)]
+        self._check(_lib.lib().rfa_demod_get_state(self._h, *[ctypes.byref(x) for x in v]), "rfa_demod_get_state")
+        return tuple(np.float32(x.value) for x in v)
+
+    def reset(self) -> None:
+        self._check(_lib.lib().rfa_demod_reset(self._h), "rfa_demod_reset")
+
+    def max_outputs(self, n_samples: int) -> int:
+        n = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_demod_max_outputs(self._h, n_samples, ctypes.byref(n)), "rfa_demod_max_outputs")
+        return n.value
+
+    # -- processing
+    def process(self, re, im, packet_samples: int | None = None) -> np.ndarray:
+        """Host planar float32 in -> float32 audio."""
+        re = np.ascontiguousarray(re, np.float32)
+        im = np.ascontiguousarray(im, np.float32)
+        if re.shape != im.shape or re.ndim != 1:
+            raise ValueError("re and im must be one-dimensional and of the same length")
+        cap = self.max_outputs(re.size)
+        out = np.empty(max(cap, 1), np.float32)
+        got = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_demod_process_host(self._h, re.ctypes.data, im.ctypes.data, re.size,
+                                                      packet_samples or 0, out.ctypes.data, cap, ctypes.byref(got)),
+                    "rfa_demod_process_host")
+        return out[:got.value].copy()
+
+    def process_device(self, re_ptr: int, im_ptr: int, n_samples: int, audio_ptr: int, capacity: int,
+                       packet_samples: int | None = None) -> int:
+        """Device pointers; asynchronous on the handle's stream; returns the audio sample count."""
+        got = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_demod_process(self._h, re_ptr, im_ptr, n_samples, packet_samples or 0, audio_ptr,
+                                                 capacity, ctypes.byref(got)), "rfa_demod_process")
+        return got.value
+
+    def set_stream(self, stream_ptr: int | None) -> None:
+        """Enqueue on exactly this hipStream_t (None: the handle's own stream)."""
+        self._check(_lib.lib().rfa_demod_set_stream(self._h, stream_ptr or None), "rfa_demod_set_stream")
+        self._stream = stream_ptr or None
+
+    def process_tensor(self, re, im, out, packet_samples: int | None = None) -> int:
+        """torch.cuda float32 tensors; runs on torch's current stream, ordered after the op that
+        produced ``re``/``im`` and before any later torch op that reads ``out``."""
+        import torch
+
+        cur = torch.cuda.current_stream(re.device).cuda_stream
+        if cur != self._stream:
+            self.set_stream(cur)
+        if re.numel() != im.numel():
+            raise ValueError("re and im must have the same length")
+        return self.process_device(re.data_ptr(), im.data_ptr(), re.numel(), out.data_ptr(), out.numel(),
+                                   packet_samples)
+
+    def synchronize(self) -> None:
+        self._check(_lib.lib().rfa_demod_synchronize(self._h), "rfa_demod_synchronize")
+
+    @property
+    def stream(self) -> int:
+        s = _lib._vp()
+        self._check(_lib.lib().rfa_demod_get_stream(self._h, ctypes.byref(s)), "rfa_demod_get_stream")
+        return s.value or 0
+
+
+class Receiver:
+    """Raw IQ bytes -> audio: ``FrontEnd(..., resampler=True)`` at the mode's quadrature rate
+    chained into a ``Demodulator``, device to device on one stream.  One ``process`` call is
+    one input packet, as the app's Scheduler feeds its Demodulator.  Changing ``mode`` retunes
+    the front end's output rate (Demodulator.kt:96-100 sets ``resampler.outputSampleRate``);
+    where the rate changes the resampler is built anew with an empty delay line, as
+    Resampler.kt:102-110 does (and, unlike the app's IQConverter, the mixer's cosine index
+    starts again with it)."""
+
+    def __init__(self, input_format: str, sample_rate: int, mode="nfm", device: int = 0):
+        import torch
+
+        self._torch = torch
+        self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
+        self._tdev = torch.device("cuda", device)
+        self.demod = Demodulator(mode, device)
+        self.front = None
+        self._freqs = None
+        self._raw = self._re = self._im = self._audio = None
+        self._cap_for = (None, 0)
+        self._retune()
+
+    def _retune(self) -> None:
+        rate = self.demod.quadrature_rate
+        if self.front is not None and self.front.output_sample_rate == rate:
+            return
+        if self.front is not None:
+            self.front.close()
+        self.front = FrontEnd(self.input_format, self.sample_rate, rate, self.device, resampler=True)
+        self.front.set_stream(self.demod.stream)
+        if self._freqs is not None:
+            self.front.set_frequencies(*self._freqs)
+
+    @property
+    def mode(self) -> int:
+        return self.demod.demodulationMode
+
+    @mode.setter
+    def mode(self, mode) -> None:
+        self.demod.demodulationMode = mode
+        self._retune()
+
+    def set_frequencies(self, frequency: int, channel_frequency: int) -> None:
+        self._freqs = (int(frequency), int(channel_frequency))
+        self.front.set_frequencies(*self._freqs)
+
+    def set_stream(self, stream_ptr: int | None) -> None:
+        """Enqueue both stages on exactly this hipStream_t (None: the demodulator's own stream)."""
+        self.demod.set_stream(stream_ptr)
+        self.front.set_stream(self.demod.stream)
+
+    def _buffers(self, nbytes: int, n: int):
+        torch = self._torch
+        if self._raw is None or self._raw.numel() < nbytes:
+            self._raw = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self._tdev)
+        if self._cap_for[0] != (n, id(self.front)):
+            self._cap_for = ((n, id(self.front)), self.front.max_outputs(n))
+        cap = self._cap_for[1]
+        if self._re is None or self._re.numel() < cap:
+            self._re = torch.empty(cap, dtype=torch.float32, device=self._tdev)
+            self._im = torch.empty(cap, dtype=torch.float32, device=self._tdev)
+            self._audio = torch.empty(cap, dtype=torch.float32, device=self._tdev)
+        return cap
+
+    def process_device(self, raw_ptr: int, n_samples: int) -> int:
+        """Raw samples at a device address -> audio left in ``self.audio_tensor``; asynchronous on
+        the receiver's stream; returns the audio sample count."""
+        cap = self._buffers(0, n_samples)
+        nq = self.front.process_device(raw_ptr, n_samples, self._re.data_ptr(), self._im.data_ptr(), cap)
+        return self.demod.process_device(self._re.data_ptr(), self._im.data_ptr(), nq, self._audio.data_ptr(), cap)
+
+    @property
+    def audio_tensor(self):
+        return self._audio
+
+    def process(self, raw_bytes) -> np.ndarray:
+        """One raw input packet (host bytes) -> float32 audio."""
+        torch = self._torch
+        buf = np.ascontiguousarray(np.frombuffer(raw_bytes, np.uint8)
+                                   if isinstance(raw_bytes, (bytes, bytearray, memoryview))
+                                   else np.asarray(raw_bytes).view(np.uint8).reshape(-1))
+        n = buf.size // BYTES_PER_SAMPLE[self.front.fmt]
+        self._buffers(buf.size, n)
+        self.demod.synchronize()                      # the staging buffer's previous use is over
+        self._raw[:buf.size].copy_(torch.from_numpy(buf.copy()))
+        torch.cuda.synchronize(self._tdev)
+        got = self.process_device(self._raw.data_ptr(), n)
+        self.demod.synchronize()
+        return self._audio[:got].cpu().numpy()
+
+    def close(self) -> None:
+        if self.front is not None:
+            self.front.close()
+            self.front = None
+        self.demod.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
