@@ -11,7 +11,10 @@ the FFT (paths relative to app/src/main/java/com/mantz_it/rfanalyzer/):
   (ui/AnalyzerSurface.kt:657,683-686,710-714);
 * exponential average -- a north-star extension with the reference's only EMA
   idiom (database/GlobalPerformanceData.kt:44-50): first frame initialises,
-  then avg += alpha*(x-avg); a -inf average is re-seeded by the next frame;
+  then avg += alpha*(x-avg).  The project owns the rule for non-finite values
+  (``ema_reseed``): a non-finite frame (NaN, +inf, -inf) makes the average
+  non-finite, and an average that is not finite is re-seeded by the next frame.
+  Peak-hold is the reference's Math.max, which propagates NaN (np.maximum);
 * channel mean dB for the squelch (analyzer/FftProcessor.kt:143-157);
 * Scheduler framing of source packets into FFT frames
   (analyzer/Scheduler.kt:252-279, source/FileIQSource.java:318-369).
@@ -40,6 +43,21 @@ def retune_shift_offset(frequency_diff: int, n: int, sample_rate: int) -> int:
     """FftProcessor.kt:143,199: ((lastF - f) * (N / sampleRate.toFloat())).toInt() in float32."""
     samples_per_hz = np.float32(n) / np.float32(sample_rate)
     return kotlin_float_to_int(np.float32(np.float32(frequency_diff) * samples_per_hz))
+
+
+def ema_reseed(ema: np.ndarray) -> np.ndarray:
+    """The EMA's rule for non-finite values, one definition for push, ema_batch and every
+    device form: where the average is not finite (uninitialised -inf, or NaN / +inf / -inf
+    left by a non-finite frame) the next frame replaces it."""
+    return ~np.isfinite(ema)
+
+
+def ema_update(ema: np.ndarray, row: np.ndarray, alpha: np.float32) -> np.ndarray:
+    """One EMA step in float32: avg += alpha (x - avg), re-seeded where ema_reseed says so.
+    A non-finite x makes a finite average non-finite by the arithmetic itself."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        upd = (ema + alpha * (row - ema)).astype(np.float32)
+    return np.where(ema_reseed(ema), row, upd).astype(np.float32)
 
 
 class FftProcessorRef:
@@ -106,10 +124,8 @@ class FftProcessorRef:
         if self.ema_alpha is not None:
             if self.ema is None or self.ema.size != n or self.freq_or_sr_changed:
                 self.ema = row.copy()
-            else:
-                reseed = ~(self.ema > -np.inf)
-                upd = (self.ema + self.ema_alpha * (row - self.ema)).astype(np.float32)
-                self.ema = np.where(reseed, row, upd).astype(np.float32)
+            else:  # a non-finite average is re-seeded by this frame (ema_reseed)
+                self.ema = ema_update(self.ema, row, self.ema_alpha)
 
     def boxcar(self, length: int) -> np.ndarray:
         """AnalyzerSurface.kt:710-714 at bin resolution: float32 running sum of the
@@ -122,16 +138,15 @@ class FftProcessorRef:
 
 
 def ema_batch(rows: np.ndarray, alpha: float, init: np.ndarray | None = None) -> np.ndarray:
-    """EMA over rows in order (extension semantics above)."""
+    """EMA over rows in order (extension semantics above): a non-finite row makes the
+    average non-finite, a non-finite average is re-seeded by the next row (ema_reseed)."""
     a = np.float32(alpha)
     ema = None if init is None else np.asarray(init, np.float32).copy()
     for row in rows:
         if ema is None:
             ema = row.astype(np.float32).copy()
             continue
-        reseed = ~(ema > -np.inf)
-        upd = (ema + a * (row - ema)).astype(np.float32)
-        ema = np.where(reseed, row, upd).astype(np.float32)
+        ema = ema_update(ema, row.astype(np.float32), a)
     return ema
 
 

@@ -117,7 +117,8 @@ int ref_loop(const void *frames, int fmt, int n, int n_frames, long frame_stride
         float *row = ring + (size_t)write_index * n;
         memcpy(row, mag, sizeof(float) * n);
         write_index = write_index == 0 ? ring_rows - 1 : write_index - 1;
-        for (int i = 0; i < n; i++) peaks[i] = fmaxf(peaks[i], row[i]);
+        /* FftProcessor.kt:241-242 is Math.max: NaN wins (fmaxf would drop it) */
+        for (int i = 0; i < n; i++) peaks[i] = (row[i] > peaks[i] || row[i] != row[i]) ? row[i] : peaks[i];
     }
     free(re); free(im); free(mag);
     pffft_destroy_setup(c.setup);

@@ -575,17 +575,42 @@ __device__ __forceinline__ void buf_store_f32x2(float2 x, rsrc_t rs, int voff, i
 }
 
 // One frame of a chunk's peak / EMA summary (the chunked scan of fft_kernels.hip
-// state_partial_kernel: pk = max, emi = the EMA started from -inf, b = the affine offset
-// of the EMA started from 0, restart = some frame was -inf).  Peak: FftProcessor.kt:241-242;
-// EMA (extension): the avg += alpha (x - avg) idiom of GlobalPerformanceData.kt:44-50.
+// state_partial_kernel: pk = max of the frames that are not NaN, nan = some frame was NaN,
+// emi = the EMA started unseeded, b = the affine offset of the EMA started from 0).
+// Peak: FftProcessor.kt:241-242; EMA (extension): the avg += alpha (x - avg) idiom of
+// GlobalPerformanceData.kt:44-50.
 // Explicit fmaf: every kernel that forms a summary (state_partial / state_fused) rounds
 // identically, so the result does not depend on which of them computed a chunk.
-RFA_HD void state_step(float &pk, float &emi, float &b, bool &restart, float x, float al) {
+//
+// Non-finite rows (one NaN or huge float sample makes a whole row NaN or +inf, a silent
+// frame is all -inf), the same rule in every state kernel and in oracle/processor.py:
+//  * peak-hold is java.lang.Math.max (FftProcessor.kt:241-242): NaN wins and stays until
+//    the peaks are reset.  (fmaxf would drop it.  Math.max also orders -0 < +0; a row never
+//    holds -0 -- db_unscaled's fma rounds an exact cancellation to +0 -- so a compare is enough.)
+//  * EMA: a non-finite frame makes the average non-finite (avg + alpha (x - avg) does that by
+//    itself), and an average that is not finite is re-seeded by the next frame.
+RFA_HD float peak_max(float pk, float x) { return (x > pk || x != x) ? x : pk; }
+RFA_HD bool state_finite(float v) { return fabsf(v) < INFINITY; }  // false for NaN, +inf, -inf
+RFA_HD float ema_step(float em, float x, float al) { return state_finite(em) ? fmaf(al, x - em, em) : x; }
+// In a frame loop peak_max is two compares and a select where fmaxf is one operation, so the
+// loops keep fmaxf and a "saw a NaN" flag (one compare; the flag is a wave mask, folded on the
+// scalar unit) and apply it once at the end: peak_end(pk, nan).  A carried peak that is NaN
+// starts the flag.  With state_restarts below the frame loop of state_fused_kernel<16> has as
+// many instructions as before the rule (profiles/state_nonfinite/bench_ab.txt).
+RFA_HD float peak_end(float pk, bool nan) { return nan ? NAN : pk; }
+RFA_HD void state_step(float &pk, bool &nan, float &emi, float &b, float x, float al) {
     pk = fmaxf(pk, x);
-    emi = (emi > -INFINITY) ? fmaf(al, x - emi, emi) : x;
-    restart |= x == -INFINITY;
+    nan |= x != x;
+    emi = ema_step(emi, x, al);
     b = fmaf(al, x - b, b);
 }
+// Did some frame of the chunk restart the EMA, i.e. was one not finite?  From that frame on the
+// average no longer depends on the one carried in (finite: it turns non-finite of the frame's
+// kind and is re-seeded by the next frame; non-finite: re-seeded at once), so the run started
+// unseeded (emi) is the result.  b answers it without a compare per frame: it starts at 0, is
+// never re-seeded, stays finite over finite frames, and once a frame made it NaN or +-inf every
+// later step leaves it non-finite (NaN stays; +-inf meets x - b = -+inf or NaN in the fma).
+RFA_HD bool state_restarts(float b) { return !state_finite(b); }
 
 // Row value 10*log10(sqrt((Re/N)^2 + (Im/N)^2)) (nativedsp.cpp:73-78) from the
 // UNSCALED FFT output x.  Scaling by 1/N is exact (power of two), so the power

@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "fft_common.h"
 #include "fft_kernels.h"
@@ -396,8 +397,11 @@ hipError_t launch_fft(const FftLaunch &a) {
 }
 
 // ----------------------------------------------------------------- state / ring kernels
-// Peak-hold (FftProcessor.kt:241-242) and EMA (extension; GlobalPerformanceData.kt:44-50
-// idiom, -inf/uninitialised state re-seeded by the next frame), frame by frame.
+// Peak-hold (FftProcessor.kt:241-242, Math.max: NaN wins) and EMA (extension;
+// GlobalPerformanceData.kt:44-50 idiom; a non-finite frame makes the average non-finite, a
+// non-finite / uninitialised average is re-seeded by the next frame), frame by frame.  The
+// rule for non-finite rows is stated once, at state_step (fft_common.h), and every form
+// below follows it.
 __device__ __forceinline__ const float *state_row(const StateLaunch &a, int f) {
     if (a.ring_rows > 0) {
         int rr = (a.ring_base - f) % a.ring_rows;
@@ -416,21 +420,23 @@ __device__ __forceinline__ int ilog2_dev(int n) { return 31 - __clz(n); }
 
 // Sequential peak-hold / EMA over the batch (one thread per bin, frames in order).
 // Peak: FftProcessor.kt:229-232.  EMA (extension): em += alpha (x - em); an
-// uninitialised (-inf) average takes the frame's value.
+// uninitialised (-inf) or otherwise non-finite average takes the frame's value.
 __global__ void state_kernel(StateLaunch a) {
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;  // storage position
     if (pos >= a.n) return;
     const int lr = state_logrs(a), bin = ring_bin(pos, lr, ring_logm(lr, ilog2_dev(a.n)));
     float pk = a.peaks ? a.peaks[bin] : 0.f;
     float em = a.ema ? a.ema[bin] : 0.f;
+    bool nan = pk != pk;
     const float al = a.ema_alpha;
 #pragma unroll 8
     for (int f = 0; f < a.n_frames; f++) {
         const float x = state_row(a, f)[pos];
         pk = fmaxf(pk, x);
-        em = (em > -INFINITY) ? em + al * (x - em) : x;
+        nan |= x != x;
+        em = ema_step(em, x, al);
     }
-    if (a.peaks) a.peaks[bin] = pk;
+    if (a.peaks) a.peaks[bin] = peak_end(pk, nan);
     if (a.ema) a.ema[bin] = em;
 }
 
@@ -456,10 +462,12 @@ __global__ void __launch_bounds__(256) state_tile_kernel(StateLaunch a) {
     }
     __syncthreads();
     float pk[SPT], em[SPT];
+    bool nan[SPT];
 #pragma unroll
     for (int j = 0; j < SPT; j++) {
         pk[j] = pk_l[l * (SB + 1) + w + 4 * j];
         em[j] = em_l[l * (SB + 1) + w + 4 * j];
+        nan[j] = pk[j] != pk[j];
     }
     const float al = a.ema_alpha;
     constexpr int FR = 8;  // frames whose loads are in flight together
@@ -479,13 +487,14 @@ __global__ void __launch_bounds__(256) state_tile_kernel(StateLaunch a) {
 #pragma unroll
             for (int j = 0; j < SPT; j++) {
                 pk[j] = fmaxf(pk[j], x[k][j]);
-                em[j] = (em[j] > -INFINITY) ? em[j] + al * (x[k][j] - em[j]) : x[k][j];
+                nan[j] |= x[k][j] != x[k][j];
+                em[j] = ema_step(em[j], x[k][j], al);
             }
         }
     }
 #pragma unroll
     for (int j = 0; j < SPT; j++) {
-        pk_l[l * (SB + 1) + w + 4 * j] = pk[j];
+        pk_l[l * (SB + 1) + w + 4 * j] = peak_end(pk[j], nan[j]);
         em_l[l * (SB + 1) + w + 4 * j] = em[j];
     }
     __syncthreads();
@@ -499,11 +508,15 @@ __global__ void __launch_bounds__(256) state_tile_kernel(StateLaunch a) {
 
 // Chunked form of the same recursions for large batches: blockIdx.y = chunk of
 // chunk_len frames.  Per (chunk, bin) it stores
-//   x: max over the chunk,
-//   y: (1-alpha)^L, or -1 if some frame of the chunk is -inf (the EMA restarts there),
+//   x: max over the chunk (NaN if a frame is NaN),
+//   y: (1-alpha)^L, or -1 if some frame of the chunk is not finite (the EMA restarts there),
 //   z: b with  em_out = y * em_in + b  for a finite em_in and no restart,
-//   w: the chunk's EMA started from -inf (= em_out whenever em_in is -inf or the
-//      chunk restarts: after a -inf frame both runs are identical).
+//   w: the chunk's EMA started unseeded (= em_out whenever em_in is not finite or the
+//      chunk restarts: from a non-finite frame on both runs are identical).
+__device__ __forceinline__ float4 state_summary(float pk, bool nan, float am, float b, float emi) {
+    return make_float4(peak_end(pk, nan), state_restarts(b) ? -1.0f : am, b, emi);
+}
+
 __global__ void state_partial_kernel(StateLaunch a, int chunk_len) {
     // 4 adjacent bins per thread: one 16-B row load per frame (N is a multiple of 64)
     const int bin = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
@@ -512,21 +525,21 @@ __global__ void state_partial_kernel(StateLaunch a, int chunk_len) {
     const int f0 = c * chunk_len, f1 = min(a.n_frames, f0 + chunk_len);
     const float al = a.ema_alpha, keep = 1.0f - al;
     float pk[4], emi[4], b[4];
-    bool restart[4];
+    bool nan[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) pk[k] = emi[k] = -INFINITY, b[k] = 0.0f, restart[k] = false;
+    for (int k = 0; k < 4; k++) pk[k] = emi[k] = -INFINITY, b[k] = 0.0f, nan[k] = false;
     float am = 1.0f;
 #pragma unroll 4
     for (int f = f0; f < f1; f++) {
         const float4 x4 = *reinterpret_cast<const float4 *>(state_row(a, f) + bin);  // storage positions
         const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
 #pragma unroll
-        for (int k = 0; k < 4; k++) state_step(pk[k], emi[k], b[k], restart[k], xs[k], al);
+        for (int k = 0; k < 4; k++) state_step(pk[k], nan[k], emi[k], b[k], xs[k], al);
         am *= keep;
     }
     float4 *out = a.part + (size_t)c * a.n + bin;
 #pragma unroll
-    for (int k = 0; k < 4; k++) out[k] = make_float4(pk[k], restart[k] ? -1.0f : am, b[k], emi[k]);
+    for (int k = 0; k < 4; k++) out[k] = state_summary(pk[k], nan[k], am, b[k], emi[k]);
 }
 
 __global__ void state_combine_kernel(StateLaunch a, int chunks) {
@@ -537,8 +550,8 @@ __global__ void state_combine_kernel(StateLaunch a, int chunks) {
     float em = a.ema ? a.ema[bin] : 0.f;
     for (int c = 0; c < chunks; c++) {
         const float4 p = a.part[(size_t)c * a.n + pos];
-        pk = fmaxf(pk, p.x);
-        em = (em == -INFINITY || p.y < 0.0f) ? p.w : fmaf(p.y, em, p.z);
+        pk = peak_max(pk, p.x);
+        em = (!state_finite(em) || p.y < 0.0f) ? p.w : fmaf(p.y, em, p.z);
     }
     if (a.peaks) a.peaks[bin] = pk;
     if (a.ema) a.ema[bin] = em;
@@ -567,14 +580,14 @@ __global__ void __launch_bounds__(256) state_fused_kernel(StateLaunch a, int chu
         const int f0 = c * chunk_len, f1 = min(a.n_frames, f0 + chunk_len);
         const float al = a.ema_alpha, keep = 1.0f - al;
         float pk[4], emi[4], b[4];
-        bool restart[4];
+        bool nan[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) pk[k] = emi[k] = -INFINITY, b[k] = 0.0f, restart[k] = false;
+        for (int k = 0; k < 4; k++) pk[k] = emi[k] = -INFINITY, b[k] = 0.0f, nan[k] = false;
         float am = 1.0f;
         auto step = [&](float4 x4) {
             const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
 #pragma unroll
-            for (int k = 0; k < 4; k++) state_step(pk[k], emi[k], b[k], restart[k], xs[k], al);
+            for (int k = 0; k < 4; k++) state_step(pk[k], nan[k], emi[k], b[k], xs[k], al);
             am *= keep;
         };
         if (RFA_STATE_BUF && a.ring_rows > 0 && (long long)a.ring_rows * a.n * 4 < (1ll << 31)) {
@@ -595,20 +608,30 @@ __global__ void __launch_bounds__(256) state_fused_kernel(StateLaunch a, int chu
             for (int f = f0; f < f1; f++) step(*reinterpret_cast<const float4 *>(state_row(a, f) + bin));  // storage positions
         }
 #pragma unroll
-        for (int k = 0; k < 4; k++) part[c][4 * l + k] = make_float4(pk[k], restart[k] ? -1.0f : am, b[k], emi[k]);
+        for (int k = 0; k < 4; k++) part[c][4 * l + k] = state_summary(pk[k], nan[k], am, b[k], emi[k]);
     }
     __syncthreads();
     const int lr = state_logrs(a), lm = ring_logm(lr, ilog2_dev(a.n));
+    // chunk_len = ceil(n_frames / CH) can leave the last chunks without a frame (300 frames:
+    // 30 chunks of 10, not 32); their unseeded summary must not re-seed a non-finite average.
+    // The fold is one wave's dependent chain at the end of every block, so the usual case --
+    // every chunk holds a frame -- takes a copy of it without that test.
+    const bool full = (CH - 1) * chunk_len < a.n_frames;
     for (int i = threadIdx.x; i < BPB; i += 256) {
         const int gb = ring_bin(blockIdx.x * BPB + i, lr, lm);  // natural bin of storage position
         float p = a.peaks ? a.peaks[gb] : 0.f;
         float em = a.ema ? a.ema[gb] : 0.f;
+        auto fold = [&](auto all) {
 #pragma unroll
-        for (int cc = 0; cc < CH; cc++) {
-            const float4 q = part[cc][i];
-            p = fmaxf(p, q.x);
-            em = (em == -INFINITY || q.y < 0.0f) ? q.w : fmaf(q.y, em, q.z);
-        }
+            for (int cc = 0; cc < CH; cc++) {
+                const bool any = decltype(all)::value || cc * chunk_len < a.n_frames;
+                const float4 q = part[cc][i];
+                p = any ? peak_max(p, q.x) : p;
+                em = !any ? em : (!state_finite(em) || q.y < 0.0f) ? q.w : fmaf(q.y, em, q.z);
+            }
+        };
+        if (full) fold(std::true_type{});
+        else fold(std::false_type{});
         if (a.peaks) a.peaks[gb] = p;
         if (a.ema) a.ema[gb] = em;
     }

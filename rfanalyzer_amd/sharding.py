@@ -30,9 +30,12 @@ def ema_partial(rows: np.ndarray, alpha: float):
     chunked device update uses (state_partial_kernel, fft_kernels.hip):
 
     ``(decay, b, fresh)`` with ``em_out = decay * em_in + b`` for a finite
-    ``em_in`` when no frame of the segment is -inf for that bin, and
-    ``em_out = fresh`` (the segment's EMA started from -inf) when ``em_in`` is
-    -inf or the segment restarts (after a -inf frame both runs coincide).
+    ``em_in`` when every frame of the segment is finite for that bin, and
+    ``em_out = fresh`` (the segment's EMA started unseeded) when ``em_in`` is
+    not finite or the segment restarts.  The rule for non-finite values is the
+    kernels' (state_step, fft_common.h): a non-finite frame (NaN, +inf, -inf)
+    makes the average non-finite, and a non-finite average is re-seeded by the
+    next frame -- so from a non-finite frame on both runs coincide.
     ``decay`` is -1 for bins that restart."""
     al = np.float32(alpha)
     keep = np.float32(1) - al
@@ -41,10 +44,10 @@ def ema_partial(rows: np.ndarray, alpha: float):
     b = np.zeros(n, np.float32)
     fresh = np.full(n, -np.inf, np.float32)
     restart = np.zeros(n, bool)
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
         for x in np.asarray(rows, np.float32):
-            fresh = np.where(fresh > -np.inf, fresh + al * (x - fresh), x).astype(np.float32)
-            restart |= np.isneginf(x)
+            fresh = np.where(np.isfinite(fresh), fresh + al * (x - fresh), x).astype(np.float32)
+            restart |= ~np.isfinite(x)
             am = (am * keep).astype(np.float32)
             b = (b + al * (x - b)).astype(np.float32)
     return np.where(restart, np.float32(-1), am), b, fresh
@@ -52,18 +55,18 @@ def ema_partial(rows: np.ndarray, alpha: float):
 
 def ema_combine(state: np.ndarray | None, segments) -> np.ndarray:
     """Fold segment summaries (from `ema_partial`) in frame order; `state`
-    None or -inf = uninitialised (the first frame seeds the average)."""
+    None or non-finite = uninitialised (the first frame seeds the average)."""
     em = None if state is None else np.asarray(state, np.float32).copy()
     for decay, b, fresh in segments:
         if em is None:
             em = np.full(b.shape, -np.inf, np.float32)
         with np.errstate(invalid="ignore"):
-            em = np.where((em == -np.inf) | (decay < 0), fresh, decay * em + b).astype(np.float32)
+            em = np.where(~np.isfinite(em) | (decay < 0), fresh, decay * em + b).astype(np.float32)
     return em
 
 
 def peak_combine(parts) -> np.ndarray:
     out = None
     for p in parts:
-        out = p.copy() if out is None else np.maximum(out, p)
+        out = p.copy() if out is None else np.maximum(out, p)  # Math.max: NaN wins
     return out

@@ -106,8 +106,8 @@ def _chunk_summaries(rows, alpha, chunk):
         with np.errstate(invalid="ignore"):
             for x in rows[c0:c0 + chunk]:
                 pk = np.maximum(pk, x)
-                emi = np.where(emi > -np.inf, emi + al * (x - emi), x).astype(np.float32)
-                restart |= np.isneginf(x)
+                emi = np.where(np.isfinite(emi), emi + al * (x - emi), x).astype(np.float32)
+                restart |= ~np.isfinite(x)
                 am = (am * keep).astype(np.float32)
                 b = (b + al * (x - b)).astype(np.float32)
         out.append((pk, np.where(restart, np.float32(-1), am), b, emi))
@@ -120,7 +120,7 @@ def _combine(state_pk, state_em, summaries):
     for p_pk, a, b, emi in summaries:
         pk = np.maximum(pk, p_pk)
         with np.errstate(invalid="ignore"):
-            em = np.where((em == -np.inf) | (a < 0), emi, a * em + b).astype(np.float32)
+            em = np.where(~np.isfinite(em) | (a < 0), emi, a * em + b).astype(np.float32)
     return pk, em
 
 

@@ -144,3 +144,62 @@ def test_config1_fixture_full_row_bar():
     st = gu.db_stats(ref64, gu.expected(spec), gu.FLOOR_PFFFT_DB)
     assert st["excluded"] < 0.001  # 2 of 15 360 bins fall below the 45 dB floor
     assert gu.full_row_diff(ref64, gu.expected(spec)) <= gu.DB_TOL
+
+
+# ---------------------------------------------------------------- the rule for non-finite rows
+def _nonfinite_rows(frames=40, n=24, seed=6):
+    """Rows of noise around -40 dB with NaN, +inf and -inf frames (whole rows and single
+    bins), at the start, adjacent, and at the end."""
+    rows = (np.random.default_rng(seed).standard_normal((frames, n)) * 10 - 40).astype(np.float32)
+    rows[0] = -np.inf
+    rows[7] = np.nan
+    rows[8] = np.inf
+    rows[15, ::3] = np.nan
+    rows[16, 1::3] = -np.inf
+    rows[22, 2::3] = np.inf
+    rows[frames - 1, :n // 2] = np.nan
+    return rows
+
+
+def test_ema_rule_for_non_finite_rows():
+    """oracle/processor.py ema_reseed: a non-finite frame makes the average non-finite (of
+    the frame's kind), and a non-finite average is re-seeded by the next frame -- so a bad
+    frame costs exactly one frame, whatever its kind.  push and ema_batch agree."""
+    a = np.float32(0.25)
+    f = np.float32
+    assert np.isnan(processor.ema_batch(np.array([[-40], [np.nan]], f), a)[0])
+    assert processor.ema_batch(np.array([[-40], [np.inf]], f), a)[0] == np.inf
+    assert processor.ema_batch(np.array([[-40], [-np.inf]], f), a)[0] == -np.inf
+    for bad in (np.nan, np.inf, -np.inf):
+        got = processor.ema_batch(np.array([[-40], [bad], [-50], [-60]], f), a)[0]
+        assert got == f(f(-50) + a * (f(-60) - f(-50)))                        # re-seeded by -50
+        assert processor.ema_batch(np.array([[bad], [bad], [-50]], f), a)[0] == f(-50)
+    rows = _nonfinite_rows()
+    p = processor.FftProcessorRef(rows.shape[1], 4, peak_hold=True, ema_alpha=0.25)
+    for k, r in enumerate(rows):
+        p.push(r, 100, 1000)
+        exp = processor.ema_batch(rows[:k + 1], 0.25)
+        np.testing.assert_array_equal(p.ema, exp)  # NaN == NaN here
+        # peak-hold is Math.max (FftProcessor.kt:241-242): NaN wins and stays
+        assert np.array_equal(np.isnan(p.peaks), np.isnan(rows[:k + 1]).any(0))
+    assert np.isnan(p.peaks).all()  # frame 7 is all NaN
+
+
+@pytest.mark.parametrize("chunk", [1, 5, 8, 9, 40])
+def test_chunked_ema_follows_the_rule_on_non_finite_rows(chunk):
+    """The chunk summaries of the device scan (rfanalyzer_amd/sharding.py restates them: a
+    non-finite frame marks the chunk as restarting, a non-finite carried average is
+    re-seeded) give the sequential recursion's non-finite pattern, for every chunk length
+    and for a NaN, +inf, -inf and finite average carried in."""
+    from rfanalyzer_amd import sharding
+    rows = _nonfinite_rows()
+    for first in (None, np.nan, np.inf, -np.inf, -33.0):
+        init = None if first is None else np.full(rows.shape[1], first, np.float32)
+        exp = processor.ema_batch(rows[1:] if first is not None else rows, 0.25, init)
+        seq = rows[1:] if first is not None else rows
+        segs = [sharding.ema_partial(seq[c:c + chunk], 0.25) for c in range(0, len(seq), chunk)]
+        got = sharding.ema_combine(init, segs)
+        for kind in (np.isnan, np.isposinf, np.isneginf):
+            assert np.array_equal(kind(got), kind(exp)), (first, kind.__name__)
+        fin = np.isfinite(exp)
+        np.testing.assert_allclose(got[fin], exp[fin], rtol=0, atol=1e-4)
