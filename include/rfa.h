@@ -23,6 +23,8 @@
  *     ui/AnalyzerSurface.kt:599-743
  *   MainViewModel scanner / squelch row reductions          rfa_row_window_stats()
  *     ui/MainViewModel.kt:861-929,1391-1540
+ *   the same reductions for every frame of a batch         rfa_set_windows(), rfa_get_window_stats(),
+ *     ui/MainViewModel.kt:861-929,1151-1250,1392-1550        rfa_ring_window_stats()
  *   IQConverter.mixPacketIntoSamplePacket + Decimator      rfa_ddc_*() (demod front end, below)
  *     source/Signed8BitIQConverter.java:53-131, analyzer/Decimator.java:175-191
  *   Resampler / RationalResampler (live demod path)        rfa_ddc_create_resampler()
@@ -216,7 +218,8 @@ RFA_API int rfa_set_ring_rows(rfa_handle *h, int32_t ring_rows);
 /* FFT size change (FftProcessor.kt:178-183 ring re-created at -9999 with
  * writeIndex = 0, :233-236 peaks re-initialised; the EMA restarts): every
  * per-N table and state buffer is rebuilt for fft_size; tuning, channel range,
- * stream and ring_rows carry over.  Synchronises. */
+ * stream and ring_rows carry over; the window list of rfa_set_windows is cleared (bin indices
+ * do not survive a size change).  Synchronises. */
 RFA_API int rfa_set_fft_size(rfa_handle *h, int32_t fft_size);
 
 /* Channel signal strength for the squelch (FftProcessor.kt:143-157): for every
@@ -279,6 +282,44 @@ RFA_API int rfa_draw_preprocess(rfa_handle *h, const rfa_draw_params *p, uint32_
  * (rfanalyzer_amd/scanner.py mirrors them).  Synchronous, host arrays. */
 RFA_API int rfa_row_window_stats(rfa_handle *h, const int32_t *lo, const int32_t *hi, size_t count, float *peak,
                                  float *avg);
+
+/* The same reductions for EVERY frame of a batch (no reference counterpart as a batch: the
+ * reference's consumers reduce one row at a time -- detectSignalsInFFT MainViewModel.kt:1463-1550,
+ * detectIEMChannelsInFFT :861-929, detectSignal / getAverageSignalLevel :1392-1457, the AirComm
+ * pair :1151-1250 -- and a 500-frame rfa_process leaves them 500 rows).
+ * rfa_set_windows keeps a list of inclusive windows [lo[i], hi[i]] over fft-shifted bins on the
+ * handle (copied to the device; validated like rfa_row_window_stats: 0 <= lo <= hi <= N - 1, else
+ * RFA_ERR_INVALID and the previous list stays).  count == 0 switches the feature off.  While a
+ * list is set, every rfa_process / rfa_process_host / rfa_process_batches (and rfa_push_packet)
+ * call also computes, for every frame f of the call and window i, peak[f][i] =
+ * FloatArray.maxOrNull() (NaN wins) and avg[f][i] = FloatArray.average().toFloat() (double sum /
+ * count, rounded once) -- what rfa_row_window_stats gives for that frame when it is the newest
+ * row (peaks identical; averages equal up to the order of the double additions, one float ulp).
+ * The work is asynchronous on the stream of the channel mean (the state stream in pipelined
+ * mode), a bounded number of launches whatever the frame and window counts, and reads the rows
+ * where the state pass reads them (caller rows, the ring when the batch fits, else a staging
+ * buffer; the ring's storage order, reverse row order and wrap are handled inside).  A value
+ * depends on its row and its window alone: the same for any split of a frame stream into calls,
+ * any row source and any other windows in the list.  The list survives retunes, resets and ring
+ * resizes; rfa_set_fft_size to another size clears it, because bin indices do not survive a size
+ * change.  At least 65536 windows are accepted.
+ * rfa_get_window_stats copies the last call's matrices, [frames][windows] in frame order and
+ * the caller's window order (at most capacity_frames frames; *frames and *windows report the
+ * full shape, 0 frames when no list is set or no call followed it), and synchronises; after
+ * rfa_process_batches it is the last batch, as for rfa_get_channel_means.
+ * rfa_get_window_stats_device returns the device matrices instead (after a join; valid until
+ * the next process call, rfa_set_windows or a size change; NULL when *frames is 0).
+ * rfa_ring_window_stats is the post-hoc form through the same kernel: the newest rows_back rows
+ * of the ring (1 <= rows_back <= ring_rows), newest first, peak / avg [rows_back][count] host
+ * arrays, synchronous; it leaves the handle's own list alone.  rows_back == 1 gives
+ * rfa_row_window_stats' peaks bit for bit. */
+RFA_API int rfa_set_windows(rfa_handle *h, const int32_t *lo, const int32_t *hi, size_t count);
+RFA_API int rfa_get_window_stats(rfa_handle *h, float *peak, float *avg, size_t capacity_frames, size_t *frames,
+                                 size_t *windows);
+RFA_API int rfa_get_window_stats_device(rfa_handle *h, const float **peak, const float **avg, size_t *frames,
+                                        size_t *windows);
+RFA_API int rfa_ring_window_stats(rfa_handle *h, const int32_t *lo, const int32_t *hi, size_t count, int32_t rows_back,
+                                  float *peak, float *avg);
 
 /* Device-side state pointers, for zero-copy consumers.  peaks and EMA are in
  * natural (fft-shifted) bin order.  The ring's rows are stored in the order

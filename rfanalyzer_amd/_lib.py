@@ -133,6 +133,15 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_draw_preprocess": (ctypes.c_int, [_h, ctypes.POINTER(RfaDrawParams), _vp, _fp, _fp, _fp]),
         "rfa_row_window_stats": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.c_size_t, _fp, _fp]),
+        "rfa_set_windows": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                           ctypes.c_size_t]),
+        "rfa_get_window_stats": (ctypes.c_int, [_h, _fp, _fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                                ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_get_window_stats_device": (ctypes.c_int, [_h, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                                       ctypes.POINTER(ctypes.c_size_t),
+                                                       ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_ring_window_stats": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                 ctypes.c_size_t, ctypes.c_int32, _fp, _fp]),
         "rfa_get_channel_means": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t,
                                                  ctypes.POINTER(ctypes.c_size_t)]),
         # demod front end (rfanalyzer_amd/demod.py)

@@ -175,6 +175,199 @@ hipError_t launch_row_windows(const float *row, int ring_logrs, int n, const int
     return hipGetLastError();
 }
 
+// The same two reductions for a window LIST and EVERY row of a batch (rfa_set_windows,
+// rfa_ring_window_stats).  A (window, frame) grid of the kernel above re-reads
+// the row once per window and starts a workgroup for a handful of loads; here a workgroup takes
+// one block of a.block_bins natural bins of one row, copies it to LDS once -- 16-B loads that walk
+// the block's STORAGE positions (WinSeg), each element dropped at its natural bin -- and then
+// reduces every window piece that lies in the block from LDS: a piece of up to kWinNarrow bins by
+// one lane in bin order, one of up to kWinWave bins by one wave (lane l takes bins lo + l,
+// lo + l + 64, ..., the 64 partials meet by the wave.h shuffles), a wider one by the workgroup
+// (thread t takes lo + t, lo + t + 256, ...; waves as before, then the four waves in order).  The host plan cuts windows at multiples of
+// win_piece_bins(), so which lanes add which bins depends on (lo, hi) alone: a window's result
+// does not depend on the rest of the list, on the frame's place in the batch or on the row
+// source.  Windows of several pieces leave (double sum, NaN-wins max) per piece and
+// window_fold_kernel adds them in bin order.  No prefix sums: rows hold -inf, +inf and NaN.
+//
+// WinSeg: the block's storage positions.  ring_pos permutes bits, so the positions of an aligned
+// block are ring_pos(base) | q with q running over a fixed bit set; counting j = 0, 4, 8, ...
+// and dealing j's bits into that set, lowest first, walks them in ascending storage order.  The
+// set is at most three runs of adjacent bits in every ring order (two for the store tiles:
+// bits 0-7 and 11 up), so q is three shift-and-mask terms.
+struct WinSeg {
+    int src[3], mask[3], dst[3];
+};
+
+__device__ __forceinline__ int win_pad(int o) { return o + (o >> 5); }  // LDS pitch 33: column-order scatters
+
+__device__ __forceinline__ void win_emit(const WinLaunch &a, int f, const int4 p, float mx, bool nan, double s) {
+    if (p.z >= 0) {
+        const size_t o = (size_t)f * a.n_windows + p.z;
+        a.peak[o] = nan ? NAN : mx;
+        a.avg[o] = (float)(s / (double)(p.y - p.x + 1));
+    } else {
+        const size_t o = (size_t)f * a.n_slots + ~p.z;
+        a.psum[o] = s;
+        a.pmax[o] = nan ? NAN : mx;
+    }
+}
+
+__global__ void __launch_bounds__(256) batch_window_kernel(WinLaunch a, WinSeg g) {
+    extern __shared__ __attribute__((aligned(16))) float win_lds[];
+    __shared__ double gs[4];
+    __shared__ float gm[4];
+    __shared__ int gn[4];
+    const int4 job = a.jobs[blockIdx.x];
+    const int end = a.jobs[blockIdx.x + 1].y;  // (the list ends with a sentinel job)
+    const int code = a.ring_rows > 0 ? a.ring_logrs : 0;
+    const int lm = ring_logm(code, 31 - __clz(a.n));
+    const int base = job.x * a.block_bins, pbase = ring_pos(base, code, lm);
+    // natural offsets of the four elements of a 16-B group
+    const int d1 = ring_bin(1, code, lm), d2 = ring_bin(2, code, lm), d3 = ring_bin(3, code, lm);
+    const int lane = threadIdx.x & 63;
+    for (int f = blockIdx.y; f < a.n_frames; f += gridDim.y) {
+        const float *row;
+        if (a.ring_rows > 0) {
+            int rr = (int)(((long long)a.ring_base + (long long)a.ring_dir * f) % a.ring_rows);
+            row = a.rows + (size_t)(rr < 0 ? rr + a.ring_rows : rr) * a.n;
+        } else {
+            row = a.rows + (size_t)((long long)f * a.row_stride);
+        }
+        for (int j = 4 * (int)threadIdx.x; j < a.block_bins; j += 4 * 256) {
+            const int q = (((j >> g.src[0]) & g.mask[0]) << g.dst[0]) | (((j >> g.src[1]) & g.mask[1]) << g.dst[1]) |
+                          (((j >> g.src[2]) & g.mask[2]) << g.dst[2]);
+            const float4 x = *reinterpret_cast<const float4 *>(row + (pbase | q));
+            const int b0 = ring_bin(q, code, lm);
+            win_lds[win_pad(b0)] = x.x;
+            win_lds[win_pad(b0 | d1)] = x.y;
+            win_lds[win_pad(b0 | d2)] = x.z;
+            win_lds[win_pad(b0 | d3)] = x.w;
+        }
+        __syncthreads();
+        for (int i = job.y + (int)threadIdx.x; i < job.z; i += 256) {  // narrow pieces: a lane each
+            const int4 p = a.pieces[i];
+            float mx = -INFINITY;
+            bool nan = false;
+            double s = 0.0;
+            for (int o = p.x - base; o <= p.y - base; o++) {
+                const float x = win_lds[win_pad(o)];
+                nan |= x != x;
+                mx = x > mx ? x : mx;
+                s += (double)x;
+            }
+            win_emit(a, f, p, mx, nan, s);
+        }
+        for (int i = job.z + (int)(threadIdx.x >> 6); i < job.w; i += 4) {  // medium pieces: a wave each
+            const int4 p = a.pieces[i];
+            float mx = -INFINITY;
+            bool nan = false;
+            double s = 0.0;
+            for (int o = p.x - base + lane; o <= p.y - base; o += 64) {
+                const float x = win_lds[win_pad(o)];
+                nan |= x != x;
+                mx = x > mx ? x : mx;
+                s += (double)x;
+            }
+            s = wave_reduce(s, [](double x, double y) { return x + y; });
+            mx = wave_reduce(mx, [](float x, float y) { return fmaxf(x, y); });
+            const int anynan = wave_reduce((int)nan, [](int x, int y) { return x | y; });
+            if (lane == 0) win_emit(a, f, p, mx, anynan != 0, s);
+        }
+        for (int i = job.w; i < end; i++) {  // wide pieces: the workgroup, as row_window_kernel
+            const int4 p = a.pieces[i];
+            float mx = -INFINITY;
+            bool nan = false;
+            double s = 0.0;
+            for (int o = p.x - base + (int)threadIdx.x; o <= p.y - base; o += 256) {
+                const float x = win_lds[win_pad(o)];
+                nan |= x != x;
+                mx = x > mx ? x : mx;
+                s += (double)x;
+            }
+            s = wave_reduce(s, [](double x, double y) { return x + y; });
+            mx = wave_reduce(mx, [](float x, float y) { return fmaxf(x, y); });
+            const int anynan = wave_reduce((int)nan, [](int x, int y) { return x | y; });
+            if (lane == 0) {
+                gs[threadIdx.x >> 6] = s;
+                gm[threadIdx.x >> 6] = mx;
+                gn[threadIdx.x >> 6] = anynan;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0)
+                win_emit(a, f, p, fmaxf(fmaxf(gm[0], gm[1]), fmaxf(gm[2], gm[3])), (gn[0] | gn[1] | gn[2] | gn[3]) != 0,
+                         ((gs[0] + gs[1]) + gs[2]) + gs[3]);
+            __syncthreads();
+        }
+        __syncthreads();  // the next row overwrites the block
+    }
+}
+
+// Windows that cross a piece boundary: their pieces' sums added in bin order, NaN-wins max.
+__global__ void __launch_bounds__(256) window_fold_kernel(WinLaunch a) {
+    const long long total = (long long)a.n_frames * a.n_folds;
+    for (long long t = blockIdx.x * 256ll + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+        const long long f = t / a.n_folds;
+        const int4 e = a.folds[(int)(t % a.n_folds)];
+        const double *ps = a.psum + (size_t)f * a.n_slots + e.y;
+        const float *pm = a.pmax + (size_t)f * a.n_slots + e.y;
+        float mx = -INFINITY;
+        bool nan = false;
+        double s = 0.0;
+        for (int i = 0; i < e.z; i++) {
+            const float x = pm[i];
+            nan |= x != x;
+            mx = x > mx ? x : mx;
+            s += ps[i];
+        }
+        const size_t o = (size_t)f * a.n_windows + e.x;
+        a.peak[o] = nan ? NAN : mx;
+        a.avg[o] = (float)(s / (double)e.w);
+    }
+}
+
+hipError_t launch_batch_windows(const WinLaunch &a) {
+    if (a.n_frames <= 0 || a.n_windows <= 0 || a.n_jobs <= 0) return hipSuccess;
+    const int code = a.ring_rows > 0 ? a.ring_logrs : 0;
+    int logn = 0, logb = 0;
+    while ((1 << logn) < a.n) logn++;
+    while ((1 << logb) < a.block_bins) logb++;
+    if ((1 << logn) != a.n || (1 << logb) != a.block_bins || a.block_bins > a.n || a.block_bins < 4)
+        return hipErrorInvalidValue;
+    // the storage bits of a block's natural bits, as runs of adjacent bits (WinSeg)
+    const int lm = ring_logm(code, logn);
+    unsigned set = 0;
+    for (int k = 0; k < logb; k++) set |= (unsigned)ring_pos(1 << k, code, lm);
+    if ((set & 3u) != 3u) return hipErrorInvalidValue;  // 16-B groups
+    WinSeg g{};
+    int runs = 0, taken = 0;
+    for (int b = 0; b < 32;) {
+        if (!(set >> b & 1u)) { b++; continue; }
+        int w = 0;
+        while (b + w < 32 && (set >> (b + w) & 1u)) w++;
+        if (runs == 3) return hipErrorInvalidValue;
+        g.src[runs] = taken;
+        g.mask[runs] = (1 << w) - 1;
+        g.dst[runs] = b;
+        runs++;
+        taken += w;
+        b += w;
+    }
+    const size_t lds = (size_t)(a.block_bins + (a.block_bins >> 5) + 1) * sizeof(float);
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&batch_window_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const int gy = a.n_frames < 32768 ? a.n_frames : 32768;
+    hipLaunchKernelGGL(batch_window_kernel, dim3(a.n_jobs, gy), dim3(256), lds, a.stream, a, g);
+    if (a.n_folds > 0) {
+        const long long total = (long long)a.n_frames * a.n_folds;
+        const int gx = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+        hipLaunchKernelGGL(window_fold_kernel, dim3(gx), dim3(256), 0, a.stream, a);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_draw(const DrawLaunch &a) {
     if (a.width <= 0 || a.ring_rows <= 0 || a.n_rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(draw_rows_kernel, dim3((a.width + 255) / 256, a.n_rows), dim3(256), 0, a.stream, a);

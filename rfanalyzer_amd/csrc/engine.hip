@@ -24,6 +24,21 @@ static constexpr size_t kStampWords = (size_t)2048 * 16 * 8;  // RFA_STAMPS_FILE
 
 using rfa::FftLaunch;
 
+// A window list on the device with the buffers its reductions write (rfa_set_windows keeps one
+// on the handle, rfa_ring_window_stats a second one for its own list).
+struct WinPlan {
+    int count = 0;                    // windows (0: off)
+    int block_bins = 0, n_jobs = 0, n_pieces = 0, n_folds = 0, n_slots = 0;
+    void *d_plan = nullptr;           // jobs | pieces | folds (int4 each)
+    size_t d_plan_cap = 0;
+    float *d_out = nullptr;           // peak [frames][count] | avg [frames][count]
+    size_t d_out_cap = 0;
+    void *d_part = nullptr;           // per-piece partials of the windows that cross a piece boundary
+    size_t d_part_cap = 0;
+    float *d_peak = nullptr, *d_avg = nullptr;  // the matrices of the last call
+    size_t frames = 0, offset = 0;    // frames the getters return, first of them (packed batches: the last batch)
+};
+
 struct rfa_handle {
     rfa_config cfg{};
     int n = 0, logn = 0;
@@ -103,6 +118,7 @@ struct rfa_handle {
     int64_t view_frequency = 0, view_sample_rate = 0;
     float view_min_db = 0.f, view_max_db = 0.f;
     size_t chan_count = 0;
+    WinPlan win, win_tmp;             // rfa_set_windows' list; rfa_ring_window_stats' list
     size_t chan_offset = 0;           // first frame of the means rfa_get_channel_means returns (packed batches: the last batch)
     int64_t last_frequency = 0, last_sample_rate = 0;
     // rfa_push_packet: the partial SamplePacket Scheduler.run fills across packets
@@ -450,6 +466,106 @@ void pipe_release(rfa_handle *h) {
     h->pipe_prev_frames = 0;
 }
 
+// Window list -> device plan (fft_kernels.h WinLaunch).  Every window is cut at the multiples
+// of win_piece_bins(), so a piece lies in one block of win_block_bins() natural bins and the
+// cut depends on (lo, hi) alone; the pieces are sorted by block, by who reduces them (a lane,
+// a wave, the workgroup), then by lo, and every non-empty block becomes one job.  A window of one piece writes its result
+// itself (out = its index in the caller's order); one of several writes a partial per piece
+// (out = ~slot, slots consecutive in bin order) and gets a fold entry.  Enqueues the upload on
+// the handle stream and waits for it.
+int plan_windows(rfa_handle *h, const int32_t *lo, const int32_t *hi, size_t count, WinPlan &p) {
+    const int n = h->n, pb = rfa::win_piece_bins(n), jb = rfa::win_block_bins(n, h->ring_logrs);
+    std::vector<int4> pcs, folds, jobs;
+    pcs.reserve(count);
+    int slots = 0;
+    for (size_t i = 0; i < count; i++) {
+        const int p0 = lo[i] / pb, p1 = hi[i] / pb;
+        if (p0 == p1) {
+            pcs.push_back(make_int4(lo[i], hi[i], (int)i, 0));
+            continue;
+        }
+        if (pcs.size() + (size_t)(p1 - p0 + 1) > ((size_t)1 << 26)) return fail(h, RFA_ERR_NOMEM, "window list too large");
+        folds.push_back(make_int4((int)i, slots, p1 - p0 + 1, hi[i] - lo[i] + 1));
+        for (int q = p0; q <= p1; q++)
+            pcs.push_back(make_int4(std::max(lo[i], q * pb), std::min(hi[i], (q + 1) * pb - 1), ~slots++, 0));
+    }
+    auto wide = [](const int4 &a) {  // who reduces the piece: a lane, a wave, the workgroup
+        const int w = a.y - a.x + 1;
+        return w <= rfa::kWinNarrow ? 0 : w <= rfa::kWinWave ? 1 : 2;
+    };
+    std::sort(pcs.begin(), pcs.end(), [&](const int4 &a, const int4 &b) {
+        const int ja = a.x / jb, jbk = b.x / jb;
+        if (ja != jbk) return ja < jbk;
+        if (wide(a) != wide(b)) return wide(a) < wide(b);
+        if (a.x != b.x) return a.x < b.x;
+        if (a.y != b.y) return a.y < b.y;
+        return a.z < b.z;
+    });
+    for (size_t i = 0; i < pcs.size();) {
+        const int blk = pcs[i].x / jb;
+        size_t w = i, g, e = i;
+        while (e < pcs.size() && pcs[e].x / jb == blk) e++;
+        while (w < e && wide(pcs[w]) < 1) w++;
+        for (g = w; g < e && wide(pcs[g]) < 2;) g++;
+        jobs.push_back(make_int4(blk, (int)i, (int)w, (int)g));
+        i = e;
+    }
+    const int n_jobs = (int)jobs.size();
+    jobs.push_back(make_int4(0, (int)pcs.size(), (int)pcs.size(), (int)pcs.size()));  // sentinel: the last job's end
+    const size_t words = jobs.size() + pcs.size() + folds.size();
+    int rc = ensure_device_buffer(h, &p.d_plan, &p.d_plan_cap, words * sizeof(int4));
+    if (rc) return rc;
+    int4 *d = static_cast<int4 *>(p.d_plan);
+    struct { const std::vector<int4> *v; size_t at; } up[] = {{&jobs, 0}, {&pcs, jobs.size()}, {&folds, jobs.size() + pcs.size()}};
+    for (auto &u : up)
+        if (!u.v->empty())
+            HIPCHK(h, hipMemcpyAsync(d + u.at, u.v->data(), u.v->size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    p.count = (int)count;
+    p.block_bins = jb;
+    p.n_jobs = n_jobs;
+    p.n_pieces = (int)pcs.size();
+    p.n_folds = (int)folds.size();
+    p.n_slots = slots;
+    p.frames = p.offset = 0;
+    return RFA_OK;
+}
+
+// Enqueue the reductions of plan p over the n_frames rows `a` addresses (rows / ring fields
+// filled by the caller) on a.stream; `busy` is a stream that may still write p's buffers.
+int run_windows(rfa_handle *h, WinPlan &p, rfa::WinLaunch a, hipStream_t busy) {
+    const size_t f = (size_t)a.n_frames, cells = f * (size_t)p.count, parts = f * (size_t)p.n_slots;
+    const size_t part_bytes = parts * (sizeof(double) + sizeof(float));
+    if (busy && (2 * cells * sizeof(float) > p.d_out_cap || part_bytes > p.d_part_cap)) HIPCHK(h, hipStreamSynchronize(busy));
+    int rc = ensure_device_buffer(h, (void **)&p.d_out, &p.d_out_cap, 2 * cells * sizeof(float));
+    if (!rc && parts) rc = ensure_device_buffer(h, &p.d_part, &p.d_part_cap, part_bytes);
+    if (rc) return rc;
+    const int4 *d = static_cast<const int4 *>(p.d_plan);
+    a.n = h->n;
+    a.n_windows = p.count;
+    a.block_bins = p.block_bins;
+    a.jobs = d;
+    a.n_jobs = p.n_jobs;
+    a.pieces = d + p.n_jobs + 1;
+    a.folds = d + p.n_jobs + 1 + p.n_pieces;
+    a.n_folds = p.n_folds;
+    a.n_slots = p.n_slots;
+    a.peak = p.d_peak = p.d_out;
+    a.avg = p.d_avg = p.d_out + cells;
+    a.psum = static_cast<double *>(p.d_part);
+    a.pmax = parts ? reinterpret_cast<float *>(static_cast<double *>(p.d_part) + parts) : nullptr;
+    HIPCHK(h, rfa::launch_batch_windows(a));
+    p.frames = f;
+    p.offset = 0;
+    return RFA_OK;
+}
+
+int check_windows(rfa_handle *h, const int32_t *lo, const int32_t *hi, size_t count) {
+    for (size_t i = 0; i < count; i++)
+        if (lo[i] < 0 || hi[i] >= h->n || lo[i] > hi[i]) return fail(h, RFA_ERR_INVALID, "window outside the row");
+    return RFA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -693,6 +809,11 @@ int rfa_destroy(rfa_handle *h) {
     hipFree(h->d_ema);
     hipFree(h->d_state_part);
     hipFree(h->d_chan);
+    for (WinPlan *p : {&h->win, &h->win_tmp}) {
+        hipFree(p->d_plan);
+        hipFree(p->d_out);
+        hipFree(p->d_part);
+    }
     hipFree(h->d_draw);
     hipFree(h->d_colors);
     hipFree(h->d_boxcar);
@@ -869,11 +990,13 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
     const bool need_chan = chan_last > chan_first;
     h->chan_count = 0;
     h->chan_offset = 0;
-    // state and channel means need the rows of the whole batch: use the caller's,
-    // else the ring when every frame lands there, else a staging buffer
+    const bool need_win = h->win.count > 0;  // rfa_set_windows
+    h->win.frames = h->win.offset = 0;
+    // state, channel means and window statistics need the rows of the whole batch: use the
+    // caller's, else the ring when every frame lands there, else a staging buffer
     float *state_rows = rows;
     bool rows_in_ring = false;
-    if ((need_state || need_chan) && !rows) {
+    if ((need_state || need_chan || need_win) && !rows) {
         if (h->d_ring && n_frames <= (size_t)h->ring_rows) {
             rows_in_ring = true;
         } else {
@@ -931,7 +1054,7 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
         HIPCHK(h, hipEventRecord(h->pipe_fft_done[par], fft_stream));
         HIPCHK(h, hipStreamWaitEvent(state_stream, h->pipe_fft_done[par], 0));
     }
-    if (need_state || need_chan) {
+    if (need_state || need_chan || need_win) {
         rfa::StateLaunch s;
         s.n = n;
         s.n_frames = (int)n_frames;
@@ -963,6 +1086,19 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
             HIPCHK(h, rfa::launch_channel_mean(s, chan_first, chan_last, h->d_chan,
                                                spans > 1 ? h->d_chan + n_frames : nullptr));
             h->chan_count = n_frames;
+        }
+        if (need_win) {  // where the channel mean goes: the same rows, the same stream
+            rfa::WinLaunch w;
+            w.rows = s.rows;
+            w.row_stride = s.row_stride;
+            w.ring_rows = s.ring_rows;
+            w.ring_base = s.ring_base;
+            w.ring_dir = -1;
+            w.ring_logrs = s.ring_logrs;
+            w.n_frames = (int)n_frames;
+            w.stream = state_stream;
+            int rc = run_windows(h, h->win, w, pipe ? state_stream : nullptr);
+            if (rc) return rc;
         }
     }
     if (pipe) {
@@ -1008,6 +1144,10 @@ int rfa_process_batches(rfa_handle *h, const void *in, size_t n_batches, size_t 
         if (!rc && h->chan_count) {  // the channel means of the last batch, as after consecutive calls
             h->chan_offset = (n_batches - 1) * frames_per_batch;
             h->chan_count = frames_per_batch;
+        }
+        if (!rc && h->win.frames) {  // likewise the window statistics
+            h->win.offset = (n_batches - 1) * frames_per_batch;
+            h->win.frames = frames_per_batch;
         }
         return rc;
     }
@@ -1255,6 +1395,79 @@ int rfa_row_window_stats(rfa_handle *h, const int32_t *lo, const int32_t *hi, si
     HIPCHK(h, rfa::launch_row_windows(row, h->ring_logrs, h->n, d_lo, d_hi, (int)count, d_pk, d_av, h->stream));
     HIPCHK(h, hipMemcpyAsync(peak, d_pk, count * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(avg, d_av, count * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RFA_OK;
+}
+
+int rfa_set_windows(rfa_handle *h, const int32_t *lo, const int32_t *hi, size_t count) {
+    if (!h || (count && (!lo || !hi)) || count > (size_t)0x7fffffff) return RFA_ERR_INVALID;
+    if (int rc = check_windows(h, lo, hi, count)) return rc;  // the previous list stays
+    int rc = set_device(h);
+    if (rc) return rc;
+    if ((rc = join(h))) return rc;  // a pipelined pass may still read the old list
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->win.count = 0;
+    h->win.frames = h->win.offset = 0;
+    if (count == 0) return RFA_OK;
+    if ((rc = plan_windows(h, lo, hi, count, h->win))) h->win.count = 0;
+    return rc;
+}
+
+int rfa_get_window_stats(rfa_handle *h, float *peak, float *avg, size_t capacity_frames, size_t *frames,
+                         size_t *windows) {
+    if (!h || !frames || !windows || (capacity_frames && (!peak || !avg))) return RFA_ERR_INVALID;
+    int rc = set_device(h);
+    if (rc) return rc;
+    if ((rc = join(h))) return rc;
+    const WinPlan &p = h->win;
+    const size_t k = std::min(capacity_frames, p.frames) * (size_t)p.count, at = p.offset * (size_t)p.count;
+    if (k) {
+        HIPCHK(h, hipMemcpyAsync(peak, p.d_peak + at, k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(avg, p.d_avg + at, k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *frames = p.frames;
+    *windows = (size_t)p.count;
+    return RFA_OK;
+}
+
+int rfa_get_window_stats_device(rfa_handle *h, const float **peak, const float **avg, size_t *frames, size_t *windows) {
+    if (!h || !peak || !avg || !frames || !windows) return RFA_ERR_INVALID;
+    int rc = set_device(h);
+    if (rc) return rc;
+    if ((rc = join(h))) return rc;  // device readers on the handle stream see the last call's matrices
+    const WinPlan &p = h->win;
+    const size_t at = p.offset * (size_t)p.count;
+    *peak = p.frames ? p.d_peak + at : nullptr;
+    *avg = p.frames ? p.d_avg + at : nullptr;
+    *frames = p.frames;
+    *windows = (size_t)p.count;
+    return RFA_OK;
+}
+
+int rfa_ring_window_stats(rfa_handle *h, const int32_t *lo, const int32_t *hi, size_t count, int32_t rows_back,
+                          float *peak, float *avg) {
+    if (!h || (count && (!lo || !hi || !peak || !avg)) || count > (size_t)0x7fffffff) return RFA_ERR_INVALID;
+    if (!h->d_ring) return fail(h, RFA_ERR_STATE, "window statistics read the ring (ring_rows > 0)");
+    if (rows_back < 1 || rows_back > h->ring_rows) return fail(h, RFA_ERR_INVALID, "rows_back outside 1..ring_rows");
+    if (int rc = check_windows(h, lo, hi, count)) return rc;
+    if (count == 0) return RFA_OK;
+    int rc = set_device(h);
+    if (rc) return rc;
+    if ((rc = join(h))) return rc;
+    if ((rc = plan_windows(h, lo, hi, count, h->win_tmp))) return rc;
+    rfa::WinLaunch w;
+    w.rows = h->d_ring;
+    w.ring_rows = h->ring_rows;
+    w.ring_base = h->read_index;  // FftProcessorData.readIndex: newest row, older ones follow it
+    w.ring_dir = 1;
+    w.ring_logrs = h->ring_logrs;
+    w.n_frames = rows_back;
+    w.stream = h->stream;
+    if ((rc = run_windows(h, h->win_tmp, w, nullptr))) return rc;
+    const size_t cells = (size_t)rows_back * count;
+    HIPCHK(h, hipMemcpyAsync(peak, h->win_tmp.d_peak, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(avg, h->win_tmp.d_avg, cells * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RFA_OK;
 }

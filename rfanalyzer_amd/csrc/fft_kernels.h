@@ -226,6 +226,40 @@ hipError_t launch_draw(const DrawLaunch &a);
 hipError_t launch_row_windows(const float *row, int ring_logrs, int n, const int *lo, const int *hi, int count,
                               float *peak, float *avg, hipStream_t s);
 
+// Peak / mean of a window list for every row of a batch (rfa_set_windows, rfa_ring_window_stats;
+// DESIGN.md §5.4b), display.hip.  The host plan (engine.hip plan_windows) cuts every window at the
+// multiples of piece_bins(), so a piece lies in one block of block_bins natural bins; a workgroup
+// stages one block of one row into LDS in natural order and reduces the block's pieces.
+// Row f is at rows + f*row_stride, or, when ring_rows > 0, at ring row
+// (ring_base + f*ring_dir) mod ring_rows (ring_dir -1: the frames of a batch, +1: newest first).
+struct WinLaunch {
+    const float *rows = nullptr;
+    long long row_stride = 0;
+    int ring_rows = 0, ring_base = 0, ring_dir = -1;
+    int ring_logrs = 0;            // ring row order (ring_pos), ring mode only
+    int n = 0, n_frames = 0;
+    int n_windows = 0;
+    int block_bins = 0;            // natural bins per job block (win_block_bins)
+    const int4 *jobs = nullptr;    // {block, first narrow piece, first wave piece, first workgroup piece};
+    int n_jobs = 0;                // a job's pieces end at the next job's first (jobs[n_jobs]: a sentinel)
+    const int4 *pieces = nullptr;  // {lo, hi, out, 0}: out >= 0 the window, else ~slot of a partial
+    const int4 *folds = nullptr;   // windows of several pieces: {window, first slot, pieces, width}
+    int n_folds = 0, n_slots = 0;
+    float *peak = nullptr, *avg = nullptr;  // [n_frames][n_windows]
+    double *psum = nullptr;        // [n_frames][n_slots]
+    float *pmax = nullptr;         // [n_frames][n_slots], NaN when the piece holds one
+    hipStream_t stream = nullptr;
+};
+constexpr int kWinNarrow = 32;     // pieces up to this many bins take one lane,
+constexpr int kWinWave = 1024;     // up to this many a wave, wider ones the workgroup
+inline int win_piece_bins(int n) { return n < 4096 ? n : 4096; }
+// a block whose storage positions are runs of whole 16-B groups in every ring order (ring_pos):
+// 4096 natural bins per residue for the 32 K .. 128 K store tiles, 4096 bins otherwise
+inline int win_block_bins(int n, int ring_code) {
+    return (ring_code & (kRingTile | kRingTile2)) ? 4096 << ring_lr(ring_code) : win_piece_bins(n);
+}
+hipError_t launch_batch_windows(const WinLaunch &a);
+
 // Ring maintenance (FftProcessor.kt:197-220) and boxcar (AnalyzerSurface.kt:710-714).
 hipError_t launch_fill(float *p, long long count, float value, hipStream_t s);
 hipError_t launch_ring_shift(const float *src, float *dst, int rows, int n, int logrs, int shift, float fill,

@@ -222,6 +222,8 @@ class SpectrumEngine:
 
     def set_fft_size(self, fft_size: int) -> None:
         """FFT size change (FftProcessor.kt:178-183): ring, peaks and EMA start over at the new N."""
+        if int(fft_size) != self.n:
+            self._win = None  # the window list does not survive a size change
         self._check(_lib.lib().rfa_set_fft_size(self._h, int(fft_size)), "rfa_set_fft_size")
         self._sync_config()
 
@@ -309,6 +311,58 @@ class SpectrumEngine:
         i32 = ctypes.POINTER(ctypes.c_int32)
         self._check(_lib.lib().rfa_row_window_stats(self._h, lo.ctypes.data_as(i32), hi.ctypes.data_as(i32), lo.size,
                                                     _fptr(pk), _fptr(av)), "rfa_row_window_stats")
+        return pk, av
+
+    @staticmethod
+    def _windows(lo, hi):
+        lo = np.ascontiguousarray(lo, dtype=np.int32).reshape(-1)
+        hi = np.ascontiguousarray(hi, dtype=np.int32).reshape(-1)
+        if lo.shape != hi.shape:
+            raise ValueError("lo and hi differ in length")
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        return lo, hi, lo.ctypes.data_as(i32), hi.ctypes.data_as(i32)
+
+    def set_windows(self, lo, hi) -> None:
+        """rfa_set_windows: keep the inclusive bin windows [lo, hi] on the handle; every later
+        process call reduces each of its frames over them (empty lists switch it off)."""
+        lo, hi, plo, phi = self._windows(lo, hi)
+        self._check(_lib.lib().rfa_set_windows(self._h, plo, phi, lo.size), "rfa_set_windows")
+        self._win = (lo.copy(), hi.copy()) if lo.size else None
+
+    def windows(self):
+        """The (lo, hi) int32 arrays set_windows last put on the handle, or None."""
+        return getattr(self, "_win", None)
+
+    def window_stats(self):
+        """(peak[B, W], avg[B, W]) of the last process call's B frames over the W windows of
+        set_windows ((0, 0) arrays when no list is set or no call followed it)."""
+        _, _, b, w = self.window_stats_device()
+        pk = np.empty((b, w), np.float32)
+        av = np.empty((b, w), np.float32)
+        fr, wn = ctypes.c_size_t(), ctypes.c_size_t()
+        self._check(_lib.lib().rfa_get_window_stats(self._h, _fptr(pk) if pk.size else None,
+                                                    _fptr(av) if av.size else None, b if pk.size else 0,
+                                                    ctypes.byref(fr), ctypes.byref(wn)), "rfa_get_window_stats")
+        return pk, av
+
+    def window_stats_device(self):
+        """(peak_ptr, avg_ptr, frames, windows): the device matrices of the last call, valid until
+        the next process call, set_windows or size change (pointers 0 when frames is 0)."""
+        pk, av = ctypes.c_void_p(), ctypes.c_void_p()
+        fr, wn = ctypes.c_size_t(), ctypes.c_size_t()
+        self._check(_lib.lib().rfa_get_window_stats_device(self._h, ctypes.byref(pk), ctypes.byref(av),
+                                                           ctypes.byref(fr), ctypes.byref(wn)),
+                    "rfa_get_window_stats_device")
+        return pk.value or 0, av.value or 0, fr.value, wn.value
+
+    def ring_window_stats(self, lo, hi, rows_back: int = 1):
+        """(peak[rows_back, W], avg[rows_back, W]) over the newest rows_back ring rows, newest
+        first (rfa_ring_window_stats); the list of set_windows is left alone."""
+        lo, hi, plo, phi = self._windows(lo, hi)
+        pk = np.empty((int(rows_back), lo.size), np.float32)
+        av = np.empty((int(rows_back), lo.size), np.float32)
+        self._check(_lib.lib().rfa_ring_window_stats(self._h, plo, phi, lo.size, int(rows_back), _fptr(pk), _fptr(av)),
+                    "rfa_ring_window_stats")
         return pk, av
 
     def main_kernel_name(self) -> str:
