@@ -29,6 +29,7 @@
  *     source/Signed8BitIQConverter.java:53-131, analyzer/Decimator.java:175-191
  *   Resampler / RationalResampler (live demod path)        rfa_ddc_create_resampler()
  *     analyzer/Resampler.kt:102-110, dsp/RationalResampler.kt:27-127
+ *   the two above for K channels of one raw packet         rfa_ddc_bank_*() (channel bank, below)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -479,6 +480,84 @@ RFA_API int rfa_resampler_design(int32_t output_rate, int32_t input_rate, int32_
                                  size_t capacity, int32_t *num_taps);
 RFA_API int rfa_lowpass_taps(float gain, float sample_rate, float cutoff, float transition, float attenuation,
                              int32_t max_taps, float *taps, size_t capacity, int32_t *num_taps);
+
+/* ------------------------------------------------------------------------
+ * Front-end channel bank: K channels out of one raw
+ * IQ stream per call.  Replaces K rfa_ddc handles fed the same bytes, i.e. K
+ * times (app paths as above)
+ *   IQConverter.mixPacketIntoSamplePacket        rfa_ddc_bank_set_frequencies() +
+ *     (one table and cosine index per slot)        rfa_ddc_bank_process()
+ *   Decimator.downsampling / Resampler.resample  rfa_ddc_bank_process()
+ *     (one filter design, one delay line per slot)
+ * The slots share input format, rates and therefore the filter (taps, ratio,
+ * decimation counter); each owns its mixer (folded frequency, table, cosine
+ * index) and its delay line.  Slot k produces, bit for bit, what an rfa_ddc
+ * handle created with the same arguments and given the same calls produces.
+ * The one deliberate difference: a slot whose mixer table would be empty
+ * (rfa_ddc_mix_info reports length 0) is rejected by
+ * rfa_ddc_bank_set_frequencies with RFA_ERR_UNSUPPORTED, where the single
+ * handle silently produces nothing and does not advance -- that slot would
+ * fall out of step with the filter clock the bank shares.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_ddc_bank rfa_ddc_bank;
+
+#define RFA_DDC_BANK_MAX_CHANNELS 1024      /* n_channels above this: RFA_ERR_INVALID */
+#define RFA_DDC_BANK_LAUNCH_CHANNELS 256    /* channels one kernel launch covers */
+
+/* resampler 0: the Decimator of rfa_ddc_create; 1: the Resampler of
+ * rfa_ddc_create_resampler.  1 <= n_channels <= RFA_DDC_BANK_MAX_CHANNELS, fixed
+ * for the bank's life.  RFA_IN_F32_INTERLEAVED is RFA_ERR_UNSUPPORTED (float
+ * input arrives mixed: every slot would be the same channel).  Arguments are
+ * checked before the device is looked for. */
+RFA_API int rfa_ddc_bank_create(int device, int input_format, int32_t sample_rate, int32_t output_sample_rate,
+                                int resampler, int32_t n_channels, rfa_ddc_bank **out);
+RFA_API int rfa_ddc_bank_destroy(rfa_ddc_bank *b);
+RFA_API const char *rfa_ddc_bank_last_error(const rfa_ddc_bank *b);
+RFA_API int rfa_ddc_bank_get_channels(const rfa_ddc_bank *b, int32_t *n_channels);
+/* rfa_ddc_set_sample_rate for every slot: all mixers become invalid; the filter
+ * is rebuilt (every delay line zeroed, counters reset) under the same
+ * conditions; on failure the old rate and filter stay. */
+RFA_API int rfa_ddc_bank_set_sample_rate(rfa_ddc_bank *b, int32_t sample_rate);
+/* rfa_ddc_set_frequencies(frequency, channel_frequency[k]) on every slot k
+ * (channel_frequency has n_channels entries): a slot whose folded mix frequency
+ * is unchanged keeps its cosine index, a changed one gets a new table and index
+ * 0; delay lines are not touched.  All or nothing: every slot's table is
+ * designed and checked first, and if one is rejected (empty table, see above)
+ * no slot changes. */
+RFA_API int rfa_ddc_bank_set_frequencies(rfa_ddc_bank *b, int64_t frequency, const int64_t *channel_frequency);
+/* Upper bound, per channel, of the outputs of one call of n_samples. */
+RFA_API int rfa_ddc_bank_max_outputs(const rfa_ddc_bank *b, size_t n_samples, size_t *n);
+/* rfa_ddc_process for every slot: out_re / out_im are [n_channels][channel_stride]
+ * device floats, slot k's outputs at k * channel_stride; *n_out is the count per
+ * channel (the same for all).  RFA_ERR_STATE until every slot has a valid mixer;
+ * RFA_ERR_SIZE when channel_stride is smaller than the count (nothing is
+ * enqueued or consumed then); input pointer rules as rfa_ddc_process.  A call
+ * too short for an output still advances delay lines and cosine indices.
+ * Asynchronous on the bank's stream; no copy, allocation or synchronisation.
+ * Up to RFA_DDC_BANK_LAUNCH_CHANNELS channels the call is two kernel launches
+ * (filter, delay lines); a larger bank takes two per group of that many. */
+RFA_API int rfa_ddc_bank_process(rfa_ddc_bank *b, const void *in, size_t n_samples, float *out_re, float *out_im,
+                                 size_t channel_stride, size_t *n_out);
+/* Same with host buffers; copies and synchronises. */
+RFA_API int rfa_ddc_bank_process_host(rfa_ddc_bank *b, const void *in, size_t n_samples, float *out_re,
+                                      float *out_im, size_t channel_stride, size_t *n_out);
+/* Slot k's mixer as rfa_ddc_get_mixer reports it; RFA_ERR_STATE while invalid. */
+RFA_API int rfa_ddc_bank_get_channel(const rfa_ddc_bank *b, int32_t k, int32_t *mix_frequency, int32_t *table_length,
+                                     int32_t *cosine_index);
+/* As rfa_ddc_get_ratio / _get_taps / _set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_ddc_bank_get_ratio(const rfa_ddc_bank *b, int32_t *interpolation, int32_t *decimation,
+                                   int32_t *taps_per_output);
+RFA_API int rfa_ddc_bank_get_taps(const rfa_ddc_bank *b, float *taps, size_t capacity, int32_t *num_taps,
+                                  int32_t *decimation);
+RFA_API int rfa_ddc_bank_set_stream(rfa_ddc_bank *b, void *stream);
+RFA_API int rfa_ddc_bank_get_stream(const rfa_ddc_bank *b, void **stream);
+RFA_API int rfa_ddc_bank_synchronize(rfa_ddc_bank *b);
+/* Host only, no device needed: the folded mix frequency and the table length
+ * rfa_ddc_set_frequencies would build for one channel (generateMixerLookupTable's
+ * fold, IQConverter.calcOptimalCosineLength, IQConverter.java:64-76).  Length 0
+ * is the empty table.  RFA_ERR_UNSUPPORTED for RFA_IN_F32_INTERLEAVED. */
+RFA_API int rfa_ddc_mix_info(int input_format, int32_t sample_rate, int64_t frequency, int64_t channel_frequency,
+                             int32_t *mix_frequency, int32_t *table_length);
 
 /* ------------------------------------------------------------------------
  * Demodulator: quadrature-rate IQ (what rfa_ddc_process writes, planar float

@@ -175,6 +175,28 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_lowpass_taps": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_int32, _fp, ctypes.c_size_t,
                                             ctypes.POINTER(ctypes.c_int32)]),
+        # front-end channel bank (rfanalyzer_amd/demod.py FrontEndBank, ReceiverBank)
+        "rfa_ddc_bank_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int, ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_ddc_bank_destroy": (ctypes.c_int, [_h]),
+        "rfa_ddc_bank_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_ddc_bank_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_ddc_bank_set_sample_rate": (ctypes.c_int, [_h, ctypes.c_int32]),
+        "rfa_ddc_bank_set_frequencies": (ctypes.c_int, [_h, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+        "rfa_ddc_bank_max_outputs": (ctypes.c_int, [_h, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_ddc_bank_process": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t,
+                                                ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_ddc_bank_process_host": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t,
+                                                     ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_ddc_bank_get_channel": (ctypes.c_int, [_h, ctypes.c_int32] + [ctypes.POINTER(ctypes.c_int32)] * 3),
+        "rfa_ddc_bank_get_ratio": (ctypes.c_int, [_h] + [ctypes.POINTER(ctypes.c_int32)] * 3),
+        "rfa_ddc_bank_get_taps": (ctypes.c_int, [_h, _fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32),
+                                                 ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_ddc_bank_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_ddc_bank_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_ddc_bank_synchronize": (ctypes.c_int, [_h]),
+        "rfa_ddc_mix_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
         # demodulator (rfanalyzer_amd/demod.py Demodulator, Receiver)
         "rfa_demod_mode_info": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_int32)] * 4),
         "rfa_bandpass_taps": (ctypes.c_int, [ctypes.c_float] * 6 + [_fp, _fp, ctypes.c_size_t,

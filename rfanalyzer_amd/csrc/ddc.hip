@@ -152,175 +152,12 @@ __device__ __forceinline__ v2f lds_ld(const v2f *p) {
 // separately rounded operations, exactly the JVM's tap * delay then +=); the
 // tap loop runs in segments that stay inside one row, so the LDS pointer just
 // walks down.
+// The body is ddc_fir_tile.inc, which ddc_bank_kernel below includes as well.
 template <int FMT>
 __global__ __launch_bounds__(kThreads) void ddc_fir_kernel(DdcLaunch a) {
-    extern __shared__ __attribute__((aligned(16))) v2f dyn[];
-    // [taps of the chunk | mixer table (cos, sin), L entries | staged samples]
-    float *wl = reinterpret_cast<float *>(dyn);
-    float2 *cs = reinterpret_cast<float2 *>(dyn + a.kc_pad / 2);
-    v2f *xs = dyn + a.kc_pad / 2 + a.cs_v2;
-    const int tid = threadIdx.x;
-    const int nth = blockDim.x;
-    for (int i = tid; i < a.L; i += nth) cs[i] = float2{a.cosv[i], a.sinv[i]};
-    __syncthreads();
-    const int D = a.D, Dp = a.D + a.pad;                   // LDS layout: rows of D samples
-    const long long m0 = (long long)blockIdx.x * a.P;
-    const int nloc = (int)min((long long)a.P, a.n_out - m0);
-    const bool valid = tid < nloc;
-    // newest input of output n (global indices), RationalResampler / FirFilter counters closed-form
-    const long long nf = a.n0 + m0, nl = nf + (nloc - 1), nt = nf + (valid ? tid : 0);
-    const long long cf = (nf * a.Dd + a.off) / a.I, cl = (nl * a.Dd + a.off) / a.I;
-    const long long pos_t = nt * a.Dd + a.off;
-    const int lane_off = (int)(pos_t / a.I - cf);          // decimator: tid * D
-    const int phase = (int)(pos_t % a.I);
-    const long long jb = cf - a.in0;                        // call-relative input index of output m0
-    const int step = a.L > 0 ? nth % a.L : 0;
-    const int srow = nth / D, scol = nth % D;
-    v2f acc = {0.0f, 0.0f};
-    for (int k0 = 0; k0 < a.T; k0 += a.KC) {
-        const int k1 = min(a.T, k0 + a.KC);
-        const long long lo = jb - (k1 - 1);                 // oldest sample any lane needs
-        const int span = (int)(cl - cf) + (k1 - k0);         // fits the LDS the host sized
-        if (a.I == 1)
-            for (int i = tid; i < k1 - k0; i += nth) wl[i] = a.taps[k0 + i];
-        // leading samples older than this call come from the history (first workgroups only)
-        const int nh = (int)min((long long)span, max(0LL, -lo));
-        for (int i = tid; i < nh; i += nth) {
-            float re, im;
-            ddc_sample<FMT>(a, lo + i, 0, re, im);
-            xs[(i / D) * Dp + i % D] = v2f{re, im};
-        }
-        // raw part: U loads in flight per lane before any is converted
-        constexpr int U = 8;
-        bool staged = false;
-        if constexpr (FMT != RFA_IN_F32_INTERLEAVED) {
-            if (a.vec4) {
-                // 4 consecutive samples per load (8 B for 8-bit IQ, 16 B for int16): four
-                // times the bytes in flight of the per-sample loop, which left HBM latency
-                // exposed.  Groups are aligned in the raw buffer; samples outside
-                // [lo + nh, lo + span) are skipped.
-                using R4 = typename Raw4Of<FMT>::type;
-                const long long gA = lo + nh, gB = lo + span;     // gA >= 0 whenever gA < gB
-                const long long q0 = gA >> 2;
-                // whole groups inside the buffer only; the last < 4 samples of the call
-                // (a group that would run past raw[S-1]) go through scalar loads below
-                const long long qend = min((gB + 3) >> 2, a.S >> 2);
-                const int nq = gA < gB ? (int)max(0LL, qend - q0) : 0;
-                const int step4 = (4 * nth) % max(a.L, 1);
-                const int srow4 = (4 * nth) / D, scol4 = (4 * nth) % D;
-                const int i0 = (int)((q0 + tid) * 4 - lo);          // may be negative for the first group
-                int tq = cos_index(a, lo + i0);
-                int rq = (i0 >= 0 ? i0 / D : -((-i0 + D - 1) / D)), cq = i0 - rq * D;
-                for (int qb = tid; qb < nq; qb += U * nth) {
-                    R4 v[U];
-#pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        const int q = qb + u * nth;
-                        if (q < nq) v[u] = static_cast<const R4 *>(a.raw)[q0 + q];
-                    }
-#pragma unroll
-                    for (int u = 0; u < U; u++) {
-                        const int q = qb + u * nth;
-                        if (q < nq) {
-                            const int ib = (int)((q0 + q) * 4 - lo);
-                            // the group's four table entries are read before any is used, so
-                            // one LDS round trip covers the group instead of four
-                            float2 cst[4];
-                            int t = tq;
-#pragma unroll
-                            for (int e = 0; e < 4; e++) {
-                                cst[e] = cs[t];
-                                if (++t >= a.L) t = 0;
-                            }
-                            int r = rq, c = cq;
-#pragma unroll
-                            for (int e = 0; e < 4; e++) {
-                                const int i = ib + e;
-                                if (i >= nh && i < span) {
-                                    float re, im;
-                                    mix_raw<FMT>(raw4_elem<FMT>(v[u], e), cst[e].x, cst[e].y, re, im);
-                                    xs[r * Dp + c] = v2f{re, im};
-                                }
-                                if (++c >= D) c = 0, r++;
-                            }
-                        }
-                        tq += step4;
-                        if (tq >= a.L) tq -= a.L;
-                        rq += srow4;
-                        cq += scol4;
-                        if (cq >= D) cq -= D, rq++;
-                    }
-                }
-                const long long gt = max(gA, (a.S >> 2) << 2);     // scalar tail [gt, gB)
-                for (long long g = gt + tid; g < gB; g += nth) {
-                    const int i = (int)(g - lo);
-                    float re, im;
-                    ddc_sample<FMT>(a, g, cos_index(a, g), re, im);
-                    xs[(i / D) * Dp + i % D] = v2f{re, im};
-                }
-                staged = true;
-            }
-        }
-        if (!staged) {
-            const int i0 = nh + tid;
-            int t = cos_index(a, lo + i0);
-            int row = i0 / D, col = i0 % D;
-            for (int base = i0; base < span; base += U * nth) {
-                typename RawOf<FMT>::type v[U];
-    #pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const int i = base + u * nth;
-                    if (i < span) v[u] = load_raw<FMT>(a, lo + i);
-                }
-    #pragma unroll
-                for (int u = 0; u < U; u++) {
-                    const int i = base + u * nth;
-                    if (i < span) {
-                        float re, im;
-                        const float2 cst = FMT == RFA_IN_F32_INTERLEAVED ? float2{0.0f, 0.0f} : cs[t];
-                        mix_raw<FMT>(v[u], cst.x, cst.y, re, im);
-                        xs[row * Dp + col] = v2f{re, im};
-                    }
-                    t += step;
-                    if (t >= a.L) t -= a.L;
-                    row += srow;
-                    col += scol;
-                    if (col >= D) col -= D, row++;
-                }
-            }
-        }
-        __syncthreads();
-        if (valid && a.pad) {
-            // decimator, even D: tap k reads staged sample tid*D + rel, rel = k1-1-k, in row segments
-            int k = k0;
-            while (k < k1) {
-                const int rel = k1 - 1 - k;
-                const int r = rel / D, c = rel - r * D;
-                const int seg = min(c + 1, k1 - k);
-                const v2f *x = xs + (tid + r) * Dp + c;
-                const float *w = wl + (k - k0);
-#pragma unroll 8
-                for (int u = 0; u < seg; u++) acc = acc + w[u] * lds_ld(x - u);
-                k += seg;
-            }
-        } else if (valid) {
-            // linear layout: one contiguous walk; taps shared (I == 1, LDS) or this lane's phase row
-            const v2f *x = xs + lane_off + (k1 - 1 - k0);
-            if (a.I == 1) {
-#pragma unroll 8
-                for (int u = 0; u < k1 - k0; u++) acc = acc + wl[u] * lds_ld(x - u);
-            } else {
-                const float *w = a.taps + (long long)phase * a.T + k0;
-#pragma unroll 8
-                for (int u = 0; u < k1 - k0; u++) acc = acc + w[u] * lds_ld(x - u);
-            }
-        }
-        __syncthreads();
-    }
-    if (valid) {
-        a.out_re[m0 + tid] = acc.x;
-        a.out_im[m0 + tid] = acc.y;
-    }
+#define DDC_TILE blockIdx.x
+#include "ddc_fir_tile.inc"
+#undef DDC_TILE
 }
 
 // new_hist[t] = sample S - (T-1) + t of the extended sequence [hist | raw].
@@ -352,6 +189,99 @@ hipError_t launch_ddc(const DdcLaunch &a, hipStream_t st) {
     }
     if (a.T > 1) {
         hipLaunchKernelGGL(ddc_hist_kernel<FMT>, dim3((a.T - 1 + kThreads - 1) / kThreads), dim3(kThreads), 0, st, a);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------- channel bank
+//
+// K channels of one raw stream per call (rfa_ddc_bank_*).  The filter -- taps,
+// I/D, the output clock n0/in0/off and therefore the tile plan -- is shared; a
+// slot owns its mixer table and cosine index, its rows of the two history
+// buffers and its output row.  Workgroup (tile, slot) runs ddc_fir_kernel's tile
+// body on a DdcLaunch whose per-slot fields were filled from the device tables,
+// so slot k computes exactly what a single handle with the same state computes.
+constexpr int kBankMaxChannels = 1024;   // rfa_ddc_bank_create's bound on n_channels
+constexpr int kBankLaunchSlots = 256;    // slots per launch; a larger bank is split into groups of this many
+
+// Written at retune only.  The cosine index of a call's first sample follows from
+// the one running input count the call passes (DdcLaunch::in0):
+// (ci_base + in0 - in_base) mod L.
+struct BankSlot {
+    int tab_off;          // floats into the table pool: [cos L | sin L]
+    int L;
+    int ci_base, pad;     // cosine index when in_base inputs had been consumed
+    long long in_base;
+};
+
+struct BankLaunch {
+    const BankSlot *slots;
+    const float *tab;
+    int slot0, nslots;                 // this launch covers slots [slot0, slot0 + nslots)
+    long long hist_pitch, out_pitch;   // floats between two slots' history / output rows
+};
+
+__device__ __forceinline__ DdcLaunch bank_slot(DdcLaunch a, const BankLaunch &b, int k) {
+    const int slot = b.slot0 + k;
+    const BankSlot s = b.slots[slot];
+    a.cosv = b.tab + s.tab_off;
+    a.sinv = a.cosv + s.L;
+    a.L = s.L;                         // a.cs_v2 stays the bank's longest table: same LDS plan for every slot
+    a.ci = (int)((s.ci_base + (a.in0 - s.in_base)) % s.L);
+    a.hist += slot * b.hist_pitch;
+    a.new_hist += slot * b.hist_pitch;
+    a.out_re += slot * b.out_pitch;
+    a.out_im += slot * b.out_pitch;
+    return a;
+}
+
+// blockIdx.x = tile * nslots + slot: the workgroups that read one raw run are
+// neighbours in dispatch order, so they run at about the same time and all but
+// the first few find the run in L2 / Infinity Cache.  (Consecutive ids go to
+// consecutive XCDs, so one run is fetched into up to 8 L2s; it is 2-4 B per
+// sample against a tap loop of T LDS reads per output.)
+template <int FMT>
+__global__ __launch_bounds__(kThreads) void ddc_bank_kernel(DdcLaunch a0, BankLaunch b) {
+    const unsigned tile = blockIdx.x / (unsigned)b.nslots;
+    const DdcLaunch a = bank_slot(a0, b, (int)(blockIdx.x - tile * (unsigned)b.nslots));
+#define DDC_TILE tile
+#include "ddc_fir_tile.inc"
+#undef DDC_TILE
+}
+
+// ddc_hist_kernel for every slot: blockIdx.y is the slot.
+template <int FMT>
+__global__ __launch_bounds__(kThreads) void ddc_bank_hist_kernel(DdcLaunch a0, BankLaunch b) {
+    const int t = blockIdx.x * kThreads + threadIdx.x;
+    if (t >= a0.T - 1) return;
+    const DdcLaunch a = bank_slot(a0, b, blockIdx.y);
+    const long long g = a.S - (a.T - 1) + t;
+    float re, im;
+    ddc_sample<FMT>(a, g, cos_index(a, g), re, im);
+    a.new_hist[t] = re;
+    a.new_hist[a.T - 1 + t] = im;
+}
+
+template <int FMT>
+hipError_t launch_ddc_bank(const DdcLaunch &a, const BankLaunch &b, hipStream_t st) {
+    if (a.n_out > 0) {
+        const long long tiles = (a.n_out + a.P - 1) / a.P;
+        static bool attr_set = false;
+        if (!attr_set) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ddc_bank_kernel<FMT>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, kDynLds);
+            if (e != hipSuccess) return e;
+            attr_set = true;
+        }
+        hipLaunchKernelGGL(ddc_bank_kernel<FMT>, dim3((unsigned)(tiles * b.nslots)), dim3(a.threads), a.lds_bytes, st,
+                           a, b);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (a.T > 1) {
+        hipLaunchKernelGGL(ddc_bank_hist_kernel<FMT>, dim3((a.T - 1 + kThreads - 1) / kThreads, b.nslots),
+                           dim3(kThreads), 0, st, a, b);
         return hipGetLastError();
     }
     return hipSuccess;
@@ -992,6 +922,346 @@ int rfa_ddc_get_mixer(const rfa_ddc *d, float *cos_t, float *sin_t, size_t capac
         if (cos_t) std::memcpy(cos_t, d->cos_t.data(), d->cos_t.size() * sizeof(float));
         if (sin_t) std::memcpy(sin_t, d->sin_t.data(), d->sin_t.size() * sizeof(float));
     }
+    return RFA_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- channel bank, host side
+
+struct rfa_ddc_bank {
+    // stream, rates, format and the shared filter (taps, I/D/T, n_done/in_done, cur) live in a
+    // single-channel handle whose own mixer and delay line stay unused
+    rfa_ddc *core = nullptr;
+    std::string err;
+    struct Slot {
+        bool valid = false;
+        int32_t cos_freq = 0;
+        int ci_base = 0;               // cosine index when in_base inputs had been consumed
+        long long in_base = 0;
+        std::vector<float> cos_t, sin_t;
+    };
+    std::vector<Slot> slots;
+    int l_max = 0;                     // longest table: sizes the LDS plan
+    float *d_tab = nullptr;            // every slot's [cos L | sin L], back to back
+    size_t tab_cap = 0;
+    BankSlot *d_slots = nullptr;
+    float *d_hist[2] = {nullptr, nullptr};   // [K][2 * (T - 1)]
+    size_t hist_cap = 0;               // floats per buffer
+    void *d_in = nullptr;              // staging of the _host entry point
+    size_t d_in_cap = 0;
+    float *d_out = nullptr;
+    size_t d_out_cap = 0;
+};
+
+namespace {
+
+int bfail(rfa_ddc_bank *b, int code, const std::string &msg) {
+    if (b) b->err = msg;
+    return code;
+}
+
+#define BHIP(b, expr)                                                                  \
+    do {                                                                               \
+        hipError_t _e = (expr);                                                        \
+        if (_e != hipSuccess) return bfail((b), RFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// status of a call made on the shared handle, with its message
+int bcore(rfa_ddc_bank *b, int rc) {
+    if (rc != RFA_OK) b->err = b->core->err;
+    return rc;
+}
+
+int bank_slot_ci(const rfa_ddc_bank *b, const rfa_ddc_bank::Slot &s) {
+    return (int)((s.ci_base + (b->core->in_done - s.in_base)) % (long long)s.cos_t.size());
+}
+
+// Zeroed delay lines for the filter the shared handle has just built.
+int bank_reset_history(rfa_ddc_bank *b) {
+    const size_t need = std::max<size_t>(1, b->slots.size() * 2 * (size_t)(b->core->T - 1));
+    if (need > b->hist_cap) {
+        for (float *&h : b->d_hist)
+            if (h) (void)hipFree(h), h = nullptr;
+        b->hist_cap = 0;
+        for (float *&h : b->d_hist)
+            if (hipMalloc(&h, need * sizeof(float)) != hipSuccess) return bfail(b, RFA_ERR_NOMEM, "hipMalloc bank history");
+        b->hist_cap = need;
+    }
+    BHIP(b, hipMemsetAsync(b->d_hist[0], 0, need * sizeof(float), b->core->stream));
+    BHIP(b, hipStreamSynchronize(b->core->stream));
+    return RFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rfa_ddc_mix_info(int input_format, int32_t sample_rate, int64_t frequency, int64_t channel_frequency,
+                     int32_t *mix_frequency, int32_t *table_length) {
+    if (ddc_sample_bytes(input_format) == 0 || sample_rate <= 0) return RFA_ERR_INVALID;
+    if (input_format == RFA_IN_F32_INTERLEAVED) return RFA_ERR_UNSUPPORTED;   // no mixer: samples arrive mixed
+    const int32_t mf = fold_mix(frequency, channel_frequency, sample_rate);
+    if (mix_frequency) *mix_frequency = mf;
+    if (table_length) *table_length = std::max(0, optimal_cosine_length(sample_rate, mf));
+    return RFA_OK;
+}
+
+int rfa_ddc_bank_create(int device, int input_format, int32_t sample_rate, int32_t output_sample_rate, int resampler,
+                        int32_t n_channels, rfa_ddc_bank **out) {
+    if (!out) return RFA_ERR_INVALID;
+    *out = nullptr;
+    if (ddc_sample_bytes(input_format) == 0 || sample_rate <= 0 || output_sample_rate <= 0) return RFA_ERR_INVALID;
+    if (resampler != 0 && resampler != 1) return RFA_ERR_INVALID;
+    if (n_channels < 1 || n_channels > kBankMaxChannels) return RFA_ERR_INVALID;
+    if (input_format == RFA_IN_F32_INTERLEAVED) return RFA_ERR_UNSUPPORTED;   // every slot would be the same channel
+    rfa_ddc_bank *b = new (std::nothrow) rfa_ddc_bank();
+    if (!b) return RFA_ERR_NOMEM;
+    int rc = ddc_create(resampler, device, input_format, sample_rate, output_sample_rate, &b->core);
+    if (rc == RFA_OK) {
+        b->slots.resize(n_channels);
+        if (hipMalloc(&b->d_slots, (size_t)n_channels * sizeof(BankSlot)) != hipSuccess) rc = RFA_ERR_NOMEM;
+        else rc = bank_reset_history(b);
+    }
+    if (rc != RFA_OK) {
+        rfa_ddc_bank_destroy(b);
+        return rc;
+    }
+    *out = b;
+    return RFA_OK;
+}
+
+int rfa_ddc_bank_destroy(rfa_ddc_bank *b) {
+    if (!b) return RFA_ERR_INVALID;
+    if (b->core) {
+        hipSetDevice(b->core->device);
+        if (b->core->stream) hipStreamSynchronize(b->core->stream);
+        for (void *p : {(void *)b->d_tab, (void *)b->d_slots, (void *)b->d_hist[0], (void *)b->d_hist[1], b->d_in,
+                        (void *)b->d_out})
+            if (p) hipFree(p);
+        rfa_ddc_destroy(b->core);
+    }
+    delete b;
+    return RFA_OK;
+}
+
+const char *rfa_ddc_bank_last_error(const rfa_ddc_bank *b) { return b ? b->err.c_str() : "null handle"; }
+
+int rfa_ddc_bank_set_stream(rfa_ddc_bank *b, void *stream) {
+    if (!b) return RFA_ERR_INVALID;
+    return bcore(b, rfa_ddc_set_stream(b->core, stream));
+}
+
+int rfa_ddc_bank_get_stream(const rfa_ddc_bank *b, void **stream) {
+    return b ? rfa_ddc_get_stream(b->core, stream) : RFA_ERR_INVALID;
+}
+
+int rfa_ddc_bank_synchronize(rfa_ddc_bank *b) {
+    if (!b) return RFA_ERR_INVALID;
+    return bcore(b, rfa_ddc_synchronize(b->core));
+}
+
+int rfa_ddc_bank_get_ratio(const rfa_ddc_bank *b, int32_t *interpolation, int32_t *decimation,
+                           int32_t *taps_per_output) {
+    return b ? rfa_ddc_get_ratio(b->core, interpolation, decimation, taps_per_output) : RFA_ERR_INVALID;
+}
+
+int rfa_ddc_bank_get_taps(const rfa_ddc_bank *b, float *taps, size_t capacity, int32_t *num_taps,
+                          int32_t *decimation) {
+    return b ? rfa_ddc_get_taps(b->core, taps, capacity, num_taps, decimation) : RFA_ERR_INVALID;
+}
+
+int rfa_ddc_bank_get_channels(const rfa_ddc_bank *b, int32_t *n_channels) {
+    if (!b || !n_channels) return RFA_ERR_INVALID;
+    *n_channels = (int32_t)b->slots.size();
+    return RFA_OK;
+}
+
+int rfa_ddc_bank_set_sample_rate(rfa_ddc_bank *b, int32_t sample_rate) {
+    if (!b || sample_rate <= 0) return RFA_ERR_INVALID;
+    rfa_ddc *d = b->core;
+    if (sample_rate == d->sample_rate) return RFA_OK;
+    // the single handle's rule: Resampler rebuilt on every rate change, Decimator when sample_rate / out changes
+    const bool rebuilt = d->mode == 1 || sample_rate / d->out_rate != d->D;
+    const int rc = bcore(b, rfa_ddc_set_sample_rate(d, sample_rate));
+    for (auto &s : b->slots) s.valid = false;   // as the handle's mixer: invalid even where the rebuild fails
+    if (rc != RFA_OK) return rc;                // old rate and filter stay
+    return rebuilt ? bank_reset_history(b) : RFA_OK;
+}
+
+int rfa_ddc_bank_set_frequencies(rfa_ddc_bank *b, int64_t frequency, const int64_t *channel_frequency) {
+    if (!b || !channel_frequency) return RFA_ERR_INVALID;
+    rfa_ddc *d = b->core;
+    const size_t K = b->slots.size();
+    // design every slot first: a rejected slot leaves the whole bank as it was
+    std::vector<rfa_ddc_bank::Slot> ns(K);
+    bool changed = false;
+    for (size_t k = 0; k < K; k++) {
+        const rfa_ddc_bank::Slot &old = b->slots[k];
+        rfa_ddc_bank::Slot &s = ns[k];
+        const int32_t mf = fold_mix(frequency, channel_frequency[k], d->sample_rate);
+        if (old.valid && mf == old.cos_freq) continue;           // keeps its table and cosine index
+        mixer_table(d->fmt, d->sample_rate, mf, s.cos_t, s.sin_t);
+        if (s.cos_t.empty())
+            return bfail(b, RFA_ERR_UNSUPPORTED, "slot " + std::to_string(k) + ": empty mixer table");
+        if (s.cos_t.size() * 8 > (size_t)kDynLds / 2)
+            return bfail(b, RFA_ERR_UNSUPPORTED, "slot " + std::to_string(k) + ": mixer table larger than half the LDS");
+        s.cos_freq = mf;
+        s.valid = changed = true;
+    }
+    if (!changed) return RFA_OK;
+    std::vector<BankSlot> desc(K);
+    std::vector<float> pool;
+    size_t l_max = 0;
+    for (size_t k = 0; k < K; k++) {
+        rfa_ddc_bank::Slot &s = ns[k];
+        if (!s.valid) {                                          // unchanged: carried over at its current index
+            s = b->slots[k];
+            s.ci_base = bank_slot_ci(b, s);
+        }
+        s.in_base = d->in_done;
+        const size_t L = s.cos_t.size();
+        desc[k] = BankSlot{(int)pool.size(), (int)L, s.ci_base, 0, s.in_base};
+        pool.insert(pool.end(), s.cos_t.begin(), s.cos_t.end());
+        pool.insert(pool.end(), s.sin_t.begin(), s.sin_t.end());
+        l_max = std::max(l_max, L);
+    }
+    BHIP(b, hipSetDevice(d->device));
+    if (pool.size() > b->tab_cap) {
+        BHIP(b, hipStreamSynchronize(d->stream));
+        float *p = nullptr;
+        if (hipMalloc(&p, pool.size() * sizeof(float)) != hipSuccess) return bfail(b, RFA_ERR_NOMEM, "hipMalloc mixer tables");
+        if (b->d_tab) (void)hipFree(b->d_tab);
+        b->d_tab = p;
+        b->tab_cap = pool.size();
+        for (auto &s : b->slots) s.valid = false;                // the old pool went with its tables
+    }
+    BHIP(b, hipMemcpyAsync(b->d_tab, pool.data(), pool.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    BHIP(b, hipMemcpyAsync(b->d_slots, desc.data(), K * sizeof(BankSlot), hipMemcpyHostToDevice, d->stream));
+    BHIP(b, hipStreamSynchronize(d->stream));
+    b->slots = std::move(ns);
+    b->l_max = (int)l_max;
+    return RFA_OK;
+}
+
+int rfa_ddc_bank_get_channel(const rfa_ddc_bank *b, int32_t k, int32_t *mix_frequency, int32_t *table_length,
+                             int32_t *cosine_index) {
+    if (!b || k < 0 || (size_t)k >= b->slots.size()) return RFA_ERR_INVALID;
+    const rfa_ddc_bank::Slot &s = b->slots[k];
+    if (!s.valid) return RFA_ERR_STATE;
+    if (mix_frequency) *mix_frequency = s.cos_freq;
+    if (table_length) *table_length = (int32_t)s.cos_t.size();
+    if (cosine_index) *cosine_index = bank_slot_ci(b, s);
+    return RFA_OK;
+}
+
+int rfa_ddc_bank_max_outputs(const rfa_ddc_bank *b, size_t n_samples, size_t *n) {
+    if (!b || !n || n_samples > (size_t)1 << 40) return RFA_ERR_INVALID;
+    const rfa_ddc *d = b->core;
+    *n = (n_samples * (size_t)d->I + (size_t)d->D - 1) / (size_t)d->D + 1;
+    return RFA_OK;
+}
+
+int rfa_ddc_bank_process(rfa_ddc_bank *b, const void *in, size_t n_samples, float *out_re, float *out_im,
+                         size_t channel_stride, size_t *n_out) {
+    if (!b || !n_out) return RFA_ERR_INVALID;
+    *n_out = 0;
+    if (n_samples == 0) return RFA_OK;
+    rfa_ddc *d = b->core;
+    const size_t sb = ddc_sample_bytes(d->fmt);
+    if (!in || (uintptr_t)in % std::min<size_t>(sb, 8) != 0) return bfail(b, RFA_ERR_INVALID, "input pointer null or misaligned");
+    if (n_samples > (size_t)1 << 40) return bfail(b, RFA_ERR_INVALID, "n_samples too large");
+    const int K = (int)b->slots.size();
+    for (const auto &s : b->slots)
+        if (!s.valid) return bfail(b, RFA_ERR_STATE, "rfa_ddc_bank_set_frequencies not called");
+    if (b->hist_cap < (size_t)K * 2 * (size_t)(d->T - 1)) return bfail(b, RFA_ERR_STATE, "no delay lines (allocation failed earlier)");
+    const long long S = (long long)n_samples;
+    const long long n = outputs_for(d, d->in_done + S) - d->n_done;
+    if ((size_t)n > channel_stride) return bfail(b, RFA_ERR_SIZE, "channel_stride smaller than the output count");
+    if (n > 0 && (!out_re || !out_im)) return RFA_ERR_INVALID;
+    BHIP(b, hipSetDevice(d->device));
+    DdcLaunch a{};
+    a.raw = in;
+    a.S = S;
+    a.hist = b->d_hist[d->cur];
+    a.new_hist = b->d_hist[d->cur ^ 1];
+    a.taps = d->d_taps;
+    a.T = d->T;
+    a.L = b->l_max;                       // the plan reserves LDS for the longest table of the bank
+    a.n0 = d->n_done;
+    a.in0 = d->in_done;
+    a.off = out_offset(d);
+    a.I = d->I;
+    a.Dd = d->D;
+    a.n_out = n;
+    plan_tiles(a);
+    a.vec4 = (uintptr_t)in % (4 * sb) == 0;
+    a.out_re = out_re;
+    a.out_im = out_im;
+    BankLaunch bl{};
+    bl.slots = b->d_slots;
+    bl.tab = b->d_tab;
+    bl.hist_pitch = 2LL * (d->T - 1);
+    bl.out_pitch = (long long)channel_stride;
+    if ((n + a.P - 1) / a.P * std::min(K, kBankLaunchSlots) > (long long)INT32_MAX)
+        return bfail(b, RFA_ERR_INVALID, "call too large for one grid");
+    for (int k0 = 0; k0 < K; k0 += kBankLaunchSlots) {
+        bl.slot0 = k0;
+        bl.nslots = std::min(kBankLaunchSlots, K - k0);
+        hipError_t e = hipSuccess;
+        switch (d->fmt) {
+        case RFA_IN_S8: e = launch_ddc_bank<RFA_IN_S8>(a, bl, d->stream); break;
+        case RFA_IN_U8: e = launch_ddc_bank<RFA_IN_U8>(a, bl, d->stream); break;
+        default: e = launch_ddc_bank<RFA_IN_S16LE>(a, bl, d->stream); break;
+        }
+        if (e != hipSuccess) return bfail(b, RFA_ERR_HIP, std::string("ddc bank launch: ") + hipGetErrorString(e));
+    }
+    if (a.T > 1) d->cur ^= 1;
+    d->n_done += n;
+    d->in_done += S;
+    *n_out = (size_t)n;
+    return RFA_OK;
+}
+
+int rfa_ddc_bank_process_host(rfa_ddc_bank *b, const void *in, size_t n_samples, float *out_re, float *out_im,
+                              size_t channel_stride, size_t *n_out) {
+    if (!b || !n_out || (n_samples && !in)) return RFA_ERR_INVALID;
+    *n_out = 0;
+    if (n_samples == 0) return RFA_OK;
+    rfa_ddc *d = b->core;
+    if (n_samples > (size_t)1 << 40) return bfail(b, RFA_ERR_INVALID, "n_samples too large");
+    BHIP(b, hipSetDevice(d->device));
+    const size_t K = b->slots.size();
+    const size_t bytes = n_samples * ddc_sample_bytes(d->fmt);
+    const size_t most = (size_t)(outputs_for(d, d->in_done + (long long)n_samples) - d->n_done);
+    if (most > channel_stride) return bfail(b, RFA_ERR_SIZE, "channel_stride smaller than the output count");
+    if (bytes > b->d_in_cap) {
+        if (b->d_in) hipFree(b->d_in);
+        b->d_in = nullptr;
+        b->d_in_cap = 0;
+        if (hipMalloc(&b->d_in, bytes) != hipSuccess) return bfail(b, RFA_ERR_NOMEM, "hipMalloc input staging");
+        b->d_in_cap = bytes;
+    }
+    const size_t pitch = most + 1;
+    if (2 * K * pitch > b->d_out_cap) {
+        if (b->d_out) hipFree(b->d_out);
+        b->d_out = nullptr;
+        b->d_out_cap = 0;
+        if (hipMalloc(&b->d_out, 2 * K * pitch * sizeof(float)) != hipSuccess) return bfail(b, RFA_ERR_NOMEM, "hipMalloc output staging");
+        b->d_out_cap = 2 * K * pitch;
+    }
+    BHIP(b, hipMemcpyAsync(b->d_in, in, bytes, hipMemcpyHostToDevice, d->stream));
+    size_t n = 0;
+    const int rc = rfa_ddc_bank_process(b, b->d_in, n_samples, b->d_out, b->d_out + K * pitch, pitch, &n);
+    if (rc != RFA_OK) return rc;
+    if (n) {
+        BHIP(b, hipMemcpy2DAsync(out_re, channel_stride * sizeof(float), b->d_out, pitch * sizeof(float),
+                                 n * sizeof(float), K, hipMemcpyDeviceToHost, d->stream));
+        BHIP(b, hipMemcpy2DAsync(out_im, channel_stride * sizeof(float), b->d_out + K * pitch, pitch * sizeof(float),
+                                 n * sizeof(float), K, hipMemcpyDeviceToHost, d->stream));
+    }
+    BHIP(b, hipStreamSynchronize(d->stream));
+    *n_out = n;
     return RFA_OK;
 }
 

@@ -22,6 +22,10 @@ HIP device every call raises.
 AudioSink's decimators (analyzer/AudioSink.java:94-97,215-237): quadrature-rate samples
 to 48 kHz audio through ``rfa_demod_*`` (``rfanalyzer_amd/csrc/demod.hip``) -- and
 ``Receiver`` chains a ``FrontEnd`` into it, raw IQ bytes to audio on one stream.
+
+``FrontEndBank`` is K front ends on one raw stream in two launches per call
+(``rfa_ddc_bank_*``): one filter, a mixer and a delay line per slot, each slot bit for bit a
+``FrontEnd``; ``ReceiverBank`` feeds one ``Demodulator`` per slot from it.
 """
 from __future__ import annotations
 
@@ -232,6 +236,160 @@ class FirFilter(FrontEnd):
         iq = np.empty(2 * re.size, np.float32)
         iq[0::2], iq[1::2] = re, im
         return self.process(iq)
+
+
+def mix_info(input_format: str, sample_rate: int, frequency: int, channel_frequency: int):
+    """(folded mix frequency, mixer table length) that ``set_frequencies`` would build for one
+    channel; length 0 is the empty table a ``FrontEndBank`` rejects.  Host-only."""
+    if input_format not in FORMATS:
+        raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
+    mf, n = ctypes.c_int32(0), ctypes.c_int32(0)
+    _lib.check(_lib.lib().rfa_ddc_mix_info(FORMATS[input_format], sample_rate, frequency, channel_frequency,
+                                           ctypes.byref(mf), ctypes.byref(n)), "rfa_ddc_mix_info")
+    return mf.value, n.value
+
+
+class FrontEndBank:
+    """``n_channels`` channels out of one raw IQ stream per call (``rfa_ddc_bank_*``): the slots
+    share format, rates and filter, each has its own mixer and delay line, and slot k gives
+    bit for bit what a ``FrontEnd`` with the same arguments and calls gives.  One call is two
+    kernel launches whatever the channel count (up to 256; two per 256 beyond).  A channel
+    whose mixer table would be empty (``mix_info`` length 0) is rejected at ``set_frequencies``."""
+
+    def __init__(self, input_format: str, sample_rate: int, output_sample_rate: int, n_channels: int,
+                 device: int = 0, resampler: bool = False):
+        if input_format not in FORMATS:
+            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
+        self._h = None
+        self.fmt = FORMATS[input_format]
+        self.output_sample_rate = output_sample_rate
+        self.resampler = resampler
+        self.n_channels = int(n_channels)
+        self._stream = None
+        h = _lib._h()
+        _lib.check(_lib.lib().rfa_ddc_bank_create(device, self.fmt, sample_rate, output_sample_rate,
+                                                  1 if resampler else 0, self.n_channels, ctypes.byref(h)),
+                   "rfa_ddc_bank_create")
+        self._h = h
+
+    # -- lifetime
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.lib().rfa_ddc_bank_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def _check(self, status: int, where: str) -> None:
+        if status != _lib.RFA_OK:
+            detail = (_lib.lib().rfa_ddc_bank_last_error(self._h) or b"").decode()
+            raise _lib.RfaError(status, where, detail)
+
+    # -- configuration
+    def set_sample_rate(self, sample_rate: int) -> None:
+        self._check(_lib.lib().rfa_ddc_bank_set_sample_rate(self._h, sample_rate), "rfa_ddc_bank_set_sample_rate")
+
+    def set_frequencies(self, frequency: int, channel_frequencies) -> None:
+        """``FrontEnd.set_frequencies(frequency, channel_frequencies[k])`` on every slot, all or
+        nothing: if one channel is rejected no slot changes."""
+        ch = [int(c) for c in channel_frequencies]
+        if len(ch) != self.n_channels:
+            raise ValueError(f"{self.n_channels} channel frequencies expected, got {len(ch)}")
+        arr = (ctypes.c_int64 * len(ch))(*ch)
+        self._check(_lib.lib().rfa_ddc_bank_set_frequencies(self._h, int(frequency), arr),
+                    "rfa_ddc_bank_set_frequencies")
+
+    def channel(self, k: int):
+        """(mix_frequency, table_length, cosine_index) of slot k's mixer."""
+        v = [ctypes.c_int32(0) for _ in range(3)]
+        self._check(_lib.lib().rfa_ddc_bank_get_channel(self._h, k, *[ctypes.byref(x) for x in v]),
+                    "rfa_ddc_bank_get_channel")
+        return tuple(x.value for x in v)
+
+    @property
+    def taps(self) -> np.ndarray:
+        n, d = ctypes.c_int32(0), ctypes.c_int32(0)
+        L = _lib.lib()
+        self._check(L.rfa_ddc_bank_get_taps(self._h, None, 0, ctypes.byref(n), ctypes.byref(d)), "get_taps")
+        out = np.empty(n.value, np.float32)
+        self._check(L.rfa_ddc_bank_get_taps(self._h, out.ctypes.data_as(_lib._fp), out.size, ctypes.byref(n),
+                                            ctypes.byref(d)), "get_taps")
+        return out
+
+    def ratio(self):
+        """(interpolation, decimation, taps per output) of the shared filter."""
+        i, d, t = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(_lib.lib().rfa_ddc_bank_get_ratio(self._h, ctypes.byref(i), ctypes.byref(d), ctypes.byref(t)),
+                    "rfa_ddc_bank_get_ratio")
+        return i.value, d.value, t.value
+
+    def max_outputs(self, n_samples: int) -> int:
+        """Upper bound of one call's outputs per channel."""
+        n = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_ddc_bank_max_outputs(self._h, n_samples, ctypes.byref(n)),
+                    "rfa_ddc_bank_max_outputs")
+        return n.value
+
+    # -- processing
+    def process(self, data):
+        """Host bytes / numpy in -> (re[K, n], im[K, n]) float32 numpy arrays."""
+        buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview))
+                                   else np.asarray(data).view(np.uint8).reshape(-1))
+        n = buf.size // BYTES_PER_SAMPLE[self.fmt]
+        cap = self.max_outputs(n)
+        re = np.empty((self.n_channels, cap), np.float32)
+        im = np.empty((self.n_channels, cap), np.float32)
+        got = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_ddc_bank_process_host(self._h, buf.ctypes.data, n, re.ctypes.data, im.ctypes.data,
+                                                         cap, ctypes.byref(got)), "rfa_ddc_bank_process_host")
+        return re[:, :got.value], im[:, :got.value]
+
+    def process_device(self, in_ptr: int, n_samples: int, re_ptr: int, im_ptr: int, channel_stride: int) -> int:
+        """Device pointers, outputs [K][channel_stride] floats; asynchronous on the bank's stream;
+        returns the output count per channel."""
+        got = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_ddc_bank_process(self._h, in_ptr, n_samples, re_ptr, im_ptr, channel_stride,
+                                                    ctypes.byref(got)), "rfa_ddc_bank_process")
+        return got.value
+
+    def process_tensor(self, raw, out_re, out_im) -> int:
+        """torch.cuda tensors: raw bytes (contiguous) -> float32 outputs of shape [K, stride], on
+        torch's current stream (see ``FrontEnd.process_tensor``)."""
+        import torch
+
+        cur = torch.cuda.current_stream(raw.device).cuda_stream
+        if cur != self._stream:
+            self.set_stream(cur)
+        n = raw.numel() * raw.element_size() // BYTES_PER_SAMPLE[self.fmt]
+        if out_re.shape != out_im.shape or out_re.dim() != 2 or out_re.shape[0] != self.n_channels:
+            raise ValueError(f"out_re and out_im must both have shape [{self.n_channels}, stride]")
+        if not (out_re.is_contiguous() and out_im.is_contiguous()):
+            raise ValueError("out_re and out_im must be contiguous")
+        return self.process_device(raw.data_ptr(), n, out_re.data_ptr(), out_im.data_ptr(), out_re.shape[1])
+
+    def set_stream(self, stream_ptr: int | None) -> None:
+        """Enqueue on exactly this hipStream_t (None: the bank's own stream)."""
+        self._check(_lib.lib().rfa_ddc_bank_set_stream(self._h, stream_ptr or None), "rfa_ddc_bank_set_stream")
+        self._stream = stream_ptr or None
+
+    def synchronize(self) -> None:
+        self._check(_lib.lib().rfa_ddc_bank_synchronize(self._h), "rfa_ddc_bank_synchronize")
+
+    @property
+    def stream(self) -> int:
+        s = _lib._vp()
+        self._check(_lib.lib().rfa_ddc_bank_get_stream(self._h, ctypes.byref(s)), "rfa_ddc_bank_get_stream")
+        return s.value or 0
 
 
 # ---------------------------------------------------------------- demodulator proper
@@ -536,6 +694,125 @@ class Receiver:
             self.front.close()
             self.front = None
         self.demod.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ReceiverBank:
+    """Raw IQ bytes -> one audio stream per channel: a ``FrontEndBank(..., resampler=True)`` at
+    the modes' quadrature rate feeding one ``Demodulator`` per slot, device to device on one
+    stream.  Slot k's audio equals, bit for bit, a ``Receiver`` in mode ``modes[k]`` tuned to
+    channel k and given the same packets.  The slots share the resampler, so every mode must
+    have the same quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``).
+    The demodulators are not banked: a packet is 2 + 4 K launches."""
+
+    def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0):
+        import torch
+
+        modes = list(modes)
+        if not modes:
+            raise ValueError("at least one mode")
+        rates = {mode_info(m)[0] for m in modes}
+        if len(rates) != 1:
+            raise ValueError(f"the modes' quadrature rates differ: {sorted(rates)}")
+        self._torch = torch
+        self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
+        self._tdev = torch.device("cuda", device)
+        self.quadrature_rate = rates.pop()
+        self.demods, self.front = [], None
+        self._raw = self._re = self._im = self._audio = None
+        self._cap_for = (None, 0)
+        try:
+            self.demods = [Demodulator(m, device) for m in modes]
+            self.front = FrontEndBank(input_format, self.sample_rate, self.quadrature_rate, len(modes), device,
+                                      resampler=True)
+            self.set_stream(None)
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def n_channels(self) -> int:
+        return len(self.demods)
+
+    def mode(self, k: int) -> int:
+        return self.demods[k].demodulationMode
+
+    def set_mode(self, k: int, mode) -> None:
+        """Slot k's DemodulationMode; only to a mode of the bank's quadrature rate."""
+        if mode_info(mode)[0] != self.quadrature_rate:
+            raise ValueError(f"mode {mode!r} has quadrature rate {mode_info(mode)[0]}, the bank runs at "
+                             f"{self.quadrature_rate}")
+        self.demods[k].demodulationMode = mode
+
+    def set_frequencies(self, frequency: int, channel_frequencies) -> None:
+        self.front.set_frequencies(frequency, channel_frequencies)
+
+    def set_stream(self, stream_ptr: int | None) -> None:
+        """Enqueue every stage on exactly this hipStream_t (None: the first demodulator's own)."""
+        self.demods[0].set_stream(stream_ptr)
+        shared = self.demods[0].stream
+        for d in self.demods[1:]:
+            d.set_stream(shared)
+        self.front.set_stream(shared)
+
+    def synchronize(self) -> None:
+        self.demods[0].synchronize()
+
+    def _buffers(self, nbytes: int, n: int) -> int:
+        torch = self._torch
+        if self._raw is None or self._raw.numel() < nbytes:
+            self._raw = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self._tdev)
+        if self._cap_for[0] != n:
+            self._cap_for = (n, self.front.max_outputs(n))
+        cap = self._cap_for[1]
+        if self._re is None or self._re.shape[1] < cap:
+            shape = (self.n_channels, cap)
+            self._re = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+            self._im = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+            self._audio = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+        return self._re.shape[1]
+
+    def process_device(self, raw_ptr: int, n_samples: int) -> list[int]:
+        """Raw samples at a device address -> audio left in the rows of ``self.audio_tensor``;
+        asynchronous on the bank's stream; returns every slot's audio sample count."""
+        cap = self._buffers(0, n_samples)
+        nq = self.front.process_device(raw_ptr, n_samples, self._re.data_ptr(), self._im.data_ptr(), cap)
+        row = 4 * cap
+        return [d.process_device(self._re.data_ptr() + k * row, self._im.data_ptr() + k * row, nq,
+                                 self._audio.data_ptr() + k * row, cap) for k, d in enumerate(self.demods)]
+
+    @property
+    def audio_tensor(self):
+        return self._audio
+
+    def process(self, raw_bytes) -> list[np.ndarray]:
+        """One raw input packet (host bytes) -> K float32 audio arrays."""
+        torch = self._torch
+        buf = np.ascontiguousarray(np.frombuffer(raw_bytes, np.uint8)
+                                   if isinstance(raw_bytes, (bytes, bytearray, memoryview))
+                                   else np.asarray(raw_bytes).view(np.uint8).reshape(-1))
+        n = buf.size // BYTES_PER_SAMPLE[self.front.fmt]
+        self._buffers(buf.size, n)
+        self.synchronize()                            # the staging buffer's previous use is over
+        self._raw[:buf.size].copy_(torch.from_numpy(buf.copy()))
+        torch.cuda.synchronize(self._tdev)
+        got = self.process_device(self._raw.data_ptr(), n)
+        self.synchronize()
+        audio = self._audio.cpu().numpy()
+        return [audio[k, :g].copy() for k, g in enumerate(got)]
+
+    def close(self) -> None:
+        if self.front is not None:
+            self.front.close()
+            self.front = None
+        for d in self.demods:
+            d.close()
+        self.demods = []
 
     def __enter__(self):
         return self
