@@ -30,6 +30,7 @@
  *   Resampler / RationalResampler (live demod path)        rfa_ddc_create_resampler()
  *     analyzer/Resampler.kt:102-110, dsp/RationalResampler.kt:27-127
  *   the two above for K channels of one raw packet         rfa_ddc_bank_*() (channel bank, below)
+ *   K Demodulators with their AudioSinks, one set of launches rfa_demod_bank_*() (demodulator bank, below)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -503,6 +504,7 @@ typedef struct rfa_ddc_bank rfa_ddc_bank;
 
 #define RFA_DDC_BANK_MAX_CHANNELS 1024      /* n_channels above this: RFA_ERR_INVALID */
 #define RFA_DDC_BANK_LAUNCH_CHANNELS 256    /* channels one kernel launch covers */
+#define RFA_DEMOD_BANK_MAX_CHANNELS 1024    /* rfa_demod_bank_create (below): n_channels above this is RFA_ERR_INVALID */
 
 /* resampler 0: the Decimator of rfa_ddc_create; 1: the Resampler of
  * rfa_ddc_create_resampler.  1 <= n_channels <= RFA_DDC_BANK_MAX_CHANNELS, fixed
@@ -639,6 +641,65 @@ RFA_API int rfa_demod_reset(rfa_demod *d);
 RFA_API int rfa_demod_set_stream(rfa_demod *d, void *stream);
 RFA_API int rfa_demod_get_stream(const rfa_demod *d, void **stream);
 RFA_API int rfa_demod_synchronize(rfa_demod *d);
+
+/* ------------------------------------------------------------------------
+ * Demodulator bank: n_channels Demodulators (each with its AudioSink) in one
+ * handle, on one stream and with one set of launches per call -- four kernels
+ * and one copy of the slots' launch records, whatever n_channels.  Slot k
+ * computes, bit for bit, what an rfa_demod handle computes when it is given the
+ * same settings and the same calls; the per-slot entries have the single
+ * handle's semantics (a mode change keeps every state, the width is coerced
+ * into the mode's limits, a reset touches that slot alone).  Modes of different
+ * quadrature rates may share a bank: it sees samples, not rates.  A slot index
+ * outside 0 .. n_channels-1 is RFA_ERR_INVALID.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_demod_bank rfa_demod_bank;
+
+/* modes[n_channels]: rfa_demod_mode of every slot; 1 <= n_channels <=
+ * RFA_DEMOD_BANK_MAX_CHANNELS.  Arguments are checked before the device is
+ * looked for: RFA_ERR_INVALID comes first, RFA_ERR_NODEVICE (with *out NULL)
+ * only for a valid request. */
+RFA_API int rfa_demod_bank_create(int device, const int32_t *modes, int32_t n_channels, rfa_demod_bank **out);
+RFA_API int rfa_demod_bank_destroy(rfa_demod_bank *b);
+RFA_API const char *rfa_demod_bank_last_error(const rfa_demod_bank *b);
+RFA_API int rfa_demod_bank_get_channels(const rfa_demod_bank *b, int32_t *n_channels);
+/* As rfa_demod_set_mode ... rfa_demod_reset, on slot k. */
+RFA_API int rfa_demod_bank_set_mode(rfa_demod_bank *b, int32_t k, int mode);
+RFA_API int rfa_demod_bank_get_mode(const rfa_demod_bank *b, int32_t k, int32_t *mode);
+RFA_API int rfa_demod_bank_set_channel_width(rfa_demod_bank *b, int32_t k, int32_t w);
+RFA_API int rfa_demod_bank_get_channel_width(const rfa_demod_bank *b, int32_t k, int32_t *w);
+RFA_API int rfa_demod_bank_set_volume(rfa_demod_bank *b, int32_t k, float v);
+RFA_API int rfa_demod_bank_set_audio_sink(rfa_demod_bank *b, int32_t k, int enable);
+RFA_API int rfa_demod_bank_get_taps(const rfa_demod_bank *b, int32_t k, int which, float *re, float *im,
+                                    size_t capacity, int32_t *num_taps, int32_t *decimation);
+RFA_API int rfa_demod_bank_get_state(rfa_demod_bank *b, int32_t k, float *last_max, float *carry_re,
+                                     float *carry_im);
+RFA_API int rfa_demod_bank_reset(rfa_demod_bank *b, int32_t k);
+/* n[n_channels]: exactly what the next rfa_demod_bank_process of n_samples would write per slot. */
+RFA_API int rfa_demod_bank_max_outputs(const rfa_demod_bank *b, size_t n_samples, size_t *n);
+/* Device pointers, asynchronous on the bank's stream.  Slot k reads n_samples
+ * floats at re + k*channel_stride and im + k*channel_stride and writes
+ * n_audio[k] floats at audio + k*audio_stride; the strides are in floats and
+ * audio_stride is every slot's capacity; channel_stride below n_samples (rows
+ * that overlap) is RFA_ERR_INVALID where n_channels > 1.  If any slot would write more, the call
+ * returns RFA_ERR_SIZE and consumes nothing in any slot.  A slot in
+ * RFA_DEMOD_OFF writes nothing, reports 0 and keeps its state.  Stale user and
+ * band-pass filters of all slots are designed first (a rejected design fails the
+ * call with no slot changed) and uploaded behind one synchronisation; a call
+ * that rebuilds nothing and grows no scratch neither allocates nor waits for the
+ * device, except for the copy of an earlier call's records where more than 8
+ * calls are queued. */
+RFA_API int rfa_demod_bank_process(rfa_demod_bank *b, const float *re, const float *im, size_t channel_stride,
+                                   size_t n_samples, size_t packet_samples, float *audio, size_t audio_stride,
+                                   size_t *n_audio /* [n_channels] */);
+/* Same with host buffers; synchronous. */
+RFA_API int rfa_demod_bank_process_host(rfa_demod_bank *b, const float *re, const float *im, size_t channel_stride,
+                                        size_t n_samples, size_t packet_samples, float *audio, size_t audio_stride,
+                                        size_t *n_audio /* [n_channels] */);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_demod_bank_set_stream(rfa_demod_bank *b, void *stream);
+RFA_API int rfa_demod_bank_get_stream(const rfa_demod_bank *b, void **stream);
+RFA_API int rfa_demod_bank_synchronize(rfa_demod_bank *b);
 
 #ifdef __cplusplus
 }

@@ -222,6 +222,31 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_demod_set_stream": (ctypes.c_int, [_h, _vp]),
         "rfa_demod_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
         "rfa_demod_synchronize": (ctypes.c_int, [_h]),
+        # demodulator bank (rfanalyzer_amd/demod.py DemodulatorBank, ReceiverBank)
+        "rfa_demod_bank_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
+                                                 ctypes.POINTER(_h)]),
+        "rfa_demod_bank_destroy": (ctypes.c_int, [_h]),
+        "rfa_demod_bank_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_demod_bank_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_demod_bank_set_mode": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_int]),
+        "rfa_demod_bank_get_mode": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_demod_bank_set_channel_width": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_int32]),
+        "rfa_demod_bank_get_channel_width": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_demod_bank_set_volume": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_float]),
+        "rfa_demod_bank_set_audio_sink": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_int]),
+        "rfa_demod_bank_get_taps": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_int, _fp, _fp, ctypes.c_size_t,
+                                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_demod_bank_get_state": (ctypes.c_int, [_h, ctypes.c_int32, _fp, _fp, _fp]),
+        "rfa_demod_bank_reset": (ctypes.c_int, [_h, ctypes.c_int32]),
+        "rfa_demod_bank_max_outputs": (ctypes.c_int, [_h, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_demod_bank_process": (ctypes.c_int, [_h, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                                  _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_demod_bank_process_host": (ctypes.c_int, [_h, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t,
+                                                       ctypes.c_size_t, _vp, ctypes.c_size_t,
+                                                       ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_demod_bank_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_demod_bank_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_demod_bank_synchronize": (ctypes.c_int, [_h]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

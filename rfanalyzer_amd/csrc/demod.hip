@@ -21,6 +21,11 @@
 // FirFilter built `in` samples ago has its newest input at n*D + off (off = D-1,
 // or 1 for D = 1: decimationCounter starts at 1).  Output counts are computed on
 // the host.  Products and sums are separately rounded in the reference's order.
+//
+// The bodies of the four kernels are the demod_*.inc files beside this one,
+// included as text: once by the kernels above and once by the demodulator bank's
+// (rfa_demod_bank_*, at the end of this file), which run K slots in one grid with
+// the slot in blockIdx.y and each slot's launch record read from a device array.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +34,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/rfa.h"
@@ -55,7 +61,7 @@ static_assert(ST_LMAX < ST_SIZE, "state layout");
 constexpr int TP_UF = 0, TP_BPR = TP_UF + kMaxUserTaps, TP_BPI = TP_BPR + kMaxBandTaps;
 constexpr int TP_A1 = TP_BPI + kMaxBandTaps, TP_A2 = TP_A1 + kMaxAudioTaps, TP_SIZE = TP_A2 + kMaxAudioTaps;
 
-enum { kKindAm = 0, kKindFm = 1, kKindBand = 2 };
+enum { kKindOff = -1, kKindAm = 0, kKindFm = 1, kKindBand = 2 };   // off: bank slots only, every block returns
 
 struct DemodLaunch {
     const float *re, *im;          // this call's input, planar
@@ -148,158 +154,55 @@ __device__ float y1_at(const DemodLaunch &a, long long r) {
 constexpr int kFlMax = (kTile - 1) * 2 + kMaxBandTaps;   // user-filtered run of a tile (decimation <= 2)
 constexpr int kInMax = kFlMax + kMaxUserTaps;
 
+// The bodies of the four kernels are .inc files included as text, shared by the single
+// handle's kernels and the bank's (the slot in blockIdx.y).
+
 __global__ __launch_bounds__(kTile) void demod_stage1_kernel(DemodLaunch a) {
-    __shared__ float xr[kInMax], xi[kInMax], fr[kFlMax], fi[kFlMax];
-    __shared__ float tu[kMaxUserTaps], tbr[kMaxBandTaps], tbi[kMaxBandTaps];
-    const int tid = threadIdx.x;
-    const long long m0 = (long long)blockIdx.x * kTile;
-    const int nloc = (int)min((long long)kTile, a.npre - m0);
-    if (tid < a.Tu) tu[tid] = a.taps[TP_UF + tid];
-    if (a.kind == kKindBand && tid < a.Tb) {
-        tbr[tid] = a.taps[TP_BPR + tid];
-        tbi[tid] = a.taps[TP_BPI + tid];
-    }
-    const long long f_first = fidx(a, m0), f_last = fidx(a, m0 + nloc - 1);
-    const int halo = a.kind == kKindBand ? a.Tb - 1 : (a.kind == kKindFm ? 1 : 0);
-    const long long flo = f_first - halo, fclo = flo < 0 ? 0 : flo;
-    const int nhist = (int)(fclo - flo);                 // samples older than this call
-    const int ncomp = (int)(f_last - fclo + 1);          // user-filtered samples to compute
-    const int nin = ncomp + a.Tu - 1;
-    const long long ilo = fclo + a.skip - (a.Tu - 1);
-    for (int i = tid; i < nin; i += kTile) {
-        float r, s;
-        in_at(a, ilo + i, r, s);
-        xr[i] = r;
-        xi[i] = s;
-    }
-    for (int j = tid; j < nhist; j += kTile) {
-        const long long f = flo + j;                      // < 0
-        if (a.kind == kKindBand) {
-            fr[j] = a.st[ST_BP_RE + a.Tb - 1 + f];
-            fi[j] = a.st[ST_BP_IM + a.Tb - 1 + f];
-        } else {                                          // FM: carryOverSamples
-            fr[j] = a.st[ST_CARRY];
-            fi[j] = a.st[ST_CARRY + 1];
-        }
-    }
-    __syncthreads();
-    for (int j = tid; j < ncomp; j += kTile) {
-        float sr = 0.0f, si = 0.0f;
-        const float *pr = xr + j + a.Tu - 1, *pi = xi + j + a.Tu - 1;
-        for (int k = 0; k < a.Tu; k++) {
-            sr = sr + tu[k] * pr[-k];
-            si = si + tu[k] * pi[-k];
-        }
-        fr[nhist + j] = sr;
-        fi[nhist + j] = si;
-    }
-    __syncthreads();
-    if (tid >= nloc) return;
-    const long long m = m0 + tid;
-    const int j = (int)(fidx(a, m) - flo);
-    float v;
-    if (a.kind == kKindAm) {
-        v = fr[j] * fr[j] + fi[j] * fi[j];
-    } else if (a.kind == kKindFm) {
-        const float cr = fr[j] * fr[j - 1] + fi[j] * fi[j - 1];
-        const float ci = fi[j] * fr[j - 1] - fr[j] * fi[j - 1];
-        v = a.qgain * (float)atan2((double)ci, (double)cr);
-    } else {
-        float s = 0.0f;                                   // only the real part is ever used
-        for (int k = 0; k < a.Tb; k++) s = s + (tbr[k] * fr[j - k] - tbi[k] * fi[j - k]);
-        v = s;
-    }
-    a.pre[m] = v;
+#define DEMOD_TILE blockIdx.x
+#include "demod_stage1_tile.inc"
+#undef DEMOD_TILE
+}
+
+// Bank kernels: the slot's record comes from a device array, read once before any
+// store (so it stays in SGPRs); the body is the single kernel's.
+__global__ __launch_bounds__(kTile) void demod_bank_stage1_kernel(const DemodLaunch *__restrict__ recs) {
+    const DemodLaunch a = recs[blockIdx.y];
+    // uniform over the block (a and blockIdx only): no lane is left at a barrier
+    if (a.kind == kKindOff || (long long)blockIdx.x * kTile >= a.npre) return;
+#define DEMOD_TILE blockIdx.x
+#include "demod_stage1_tile.inc"
+#undef DEMOD_TILE
 }
 
 // ---------------------------------------------------------------- kernel 2: per-packet maximum and sum
 
+
 __global__ __launch_bounds__(64) void demod_packet_kernel(DemodLaunch a) {
-    __shared__ float buf[64];
-    const long long p = blockIdx.x;
-    const int lane = threadIdx.x;
-    const long long X0 = p * a.ps, X1 = min((p + 1) * a.ps, a.n);
-    const long long lo = pre_lower(a, X0), hi = pre_lower(a, X1);
-    float m = -INFINITY;
-    for (long long q = lo + lane; q < hi; q += 64) {
-        const float x = a.pre[q];
-        if (x > m) m = x;                                 // NaN never wins, as in the reference
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float o = __shfl_xor(m, off);
-        if (o > m) m = o;
-    }
-    float avg = 0.0f;
-    if (a.kind == kKindAm) {
-        float s = 0.0f;
-        for (long long base = lo; base < hi; base += 64) {
-            buf[lane] = base + lane < hi ? a.pre[base + lane] : 0.0f;
-            __syncthreads();
-            if (lane == 0) {
-                const int cnt = (int)min(64LL, hi - base);
-                for (int j = 0; j < cnt; j++) s = s + buf[j];
-            }
-            __syncthreads();
-        }
-        avg = s / (float)(int)(hi - lo);
-    }
-    if (lane == 0) {
-        a.pk_max[p] = m;
-        a.pk_avg[p] = avg;
-    }
+#define DEMOD_TILE blockIdx.x
+#include "demod_packet_wave.inc"
+#undef DEMOD_TILE
+}
+
+__global__ __launch_bounds__(64) void demod_bank_packet_kernel(const DemodLaunch *__restrict__ recs) {
+    const DemodLaunch a = recs[blockIdx.y];
+    // uniform over the block: slots that are off or without AGC (the FM kinds), packets past the slot's
+    if (a.kind == kKindOff || !a.agc || (long long)blockIdx.x >= a.K) return;
+#define DEMOD_TILE blockIdx.x
+#include "demod_packet_wave.inc"
+#undef DEMOD_TILE
 }
 
 // ---------------------------------------------------------------- kernel 3: state for the next call
 
+
 __global__ __launch_bounds__(kTile) void demod_state_kernel(DemodLaunch a) {
-    const int t = threadIdx.x;
-    if (t == 0) {
-        float lm = a.st[ST_LMAX];
-        if (a.agc) {
-            for (long long p = 0; p < a.K; p++) {
-                lm = lm * 0.95f;
-                const float m = a.pk_max[p];
-                if (m > lm) lm = m;
-                a.pk_gain[p] = 0.75f / lm;
-            }
-        }
-        a.nst[ST_LMAX] = lm;
-    }
-    if (t < kMaxUserTaps) {
-        float r = 0.0f, s = 0.0f;
-        if (t < a.Tu - 1) in_at(a, a.n - (a.Tu - 1) + t, r, s);
-        a.nst[ST_UF_RE + t] = r;
-        a.nst[ST_UF_IM + t] = s;
-    }
-    if (t < kMaxBandTaps) {
-        float r = a.st[ST_BP_RE + t], s = a.st[ST_BP_IM + t];
-        if (a.kind == kKindBand && t < a.Tb - 1) {
-            const long long f = a.F - (a.Tb - 1) + t;
-            if (f < 0) {
-                r = a.st[ST_BP_RE + a.Tb - 1 + f];
-                s = a.st[ST_BP_IM + a.Tb - 1 + f];
-            } else {
-                filt_at(a, f, r, s);
-            }
-        }
-        a.nst[ST_BP_RE + t] = r;
-        a.nst[ST_BP_IM + t] = s;
-    }
-    if (t == 0) {
-        float r = a.st[ST_CARRY], s = a.st[ST_CARRY + 1];
-        if (a.kind == kKindFm && a.F > 0) filt_at(a, a.F - 1, r, s);
-        a.nst[ST_CARRY] = r;
-        a.nst[ST_CARRY + 1] = s;
-    }
-    __syncthreads();                                      // the gains of this call are written
-    if (t < kMaxAudioTaps) {
-        float v = a.st[ST_A1 + t];
-        if (a.sink >= 1 && t < a.T1 - 1) v = v_at(a, a.npre - (a.T1 - 1) + t);
-        a.nst[ST_A1 + t] = v;
-        float y = a.st[ST_A2 + t];
-        if (a.sink == 2 && t < a.T2 - 1) y = y1_at(a, a.ny1 - (a.T2 - 1) + t);
-        a.nst[ST_A2 + t] = y;
-    }
+#include "demod_state_block.inc"
+}
+
+__global__ __launch_bounds__(kTile) void demod_bank_state_kernel(const DemodLaunch *__restrict__ recs) {
+    const DemodLaunch a = recs[blockIdx.x];
+    if (a.kind == kKindOff) return;                       // uniform over the block; the slot's state stays
+#include "demod_state_block.inc"
 }
 
 // ---------------------------------------------------------------- kernel 4: gain, volume, audio FIRs
@@ -307,53 +210,20 @@ __global__ __launch_bounds__(kTile) void demod_state_kernel(DemodLaunch a) {
 constexpr int kY1Max = (kTile - 1) * kA2Dec + kMaxAudioTaps;
 constexpr int kVMax = (kY1Max - 1) * kA1Dec + kMaxAudioTaps;
 
+
 __global__ __launch_bounds__(kTile) void demod_audio_kernel(DemodLaunch a) {
-    __shared__ float vb[kVMax], yb[kY1Max], t1[kMaxAudioTaps], t2[kMaxAudioTaps];
-    const int tid = threadIdx.x;
-    const long long o0 = (long long)blockIdx.x * kTile;
-    const int nloc = (int)min((long long)kTile, a.n_audio - o0);
-    if (a.sink == 0) {
-        if (tid < nloc) a.out[o0 + tid] = v_at(a, o0 + tid);
-        return;
-    }
-    if (tid < a.T1) t1[tid] = a.taps[TP_A1 + tid];
-    if (tid < a.T2) t2[tid] = a.taps[TP_A2 + tid];
-    if (a.sink == 1) {
-        const long long clo = c1_of(a, o0) - (a.T1 - 1), chi = c1_of(a, o0 + nloc - 1);
-        const int nv = (int)(chi - clo + 1);
-        for (int i = tid; i < nv; i += kTile) vb[i] = v_at(a, clo + i);
-        __syncthreads();
-        if (tid < nloc) {
-            const float *x = vb + (int)(c1_of(a, o0 + tid) - clo);
-            float s = 0.0f;
-            for (int k = 0; k < a.T1; k++) s = s + t1[k] * x[-k];
-            a.out[o0 + tid] = s;
-        }
-        return;
-    }
-    // audioFilter2 output o has its newest input at audioFilter1 output r(o) of this call
-    const long long r_first = (a.a2_out0 + o0) * kA2Dec + (kA2Dec - 1) - a.a2_in0;
-    const long long rlo = r_first - (a.T2 - 1), rhi = r_first + (long long)(nloc - 1) * kA2Dec;
-    const long long rclo = rlo < 0 ? 0 : rlo;
-    const int nhist = (int)(rclo - rlo), nr = (int)(rhi - rlo + 1);
-    const long long vlo = c1_of(a, rclo) - (a.T1 - 1), vhi = c1_of(a, rhi);
-    const int nv = (int)(vhi - vlo + 1);
-    for (int i = tid; i < nv; i += kTile) vb[i] = v_at(a, vlo + i);
-    for (int j = tid; j < nhist; j += kTile) yb[j] = a.st[ST_A2 + a.T2 - 1 + rlo + j];
-    __syncthreads();
-    for (int j = nhist + tid; j < nr; j += kTile) {
-        const float *x = vb + (int)(c1_of(a, rlo + j) - vlo);
-        float s = 0.0f;
-        for (int k = 0; k < a.T1; k++) s = s + t1[k] * x[-k];
-        yb[j] = s;
-    }
-    __syncthreads();
-    if (tid < nloc) {
-        const float *y = yb + (a.T2 - 1) + tid * kA2Dec;
-        float s = 0.0f;
-        for (int k = 0; k < a.T2; k++) s = s + t2[k] * y[-k];
-        a.out[o0 + tid] = s;
-    }
+#define DEMOD_TILE blockIdx.x
+#include "demod_audio_tile.inc"
+#undef DEMOD_TILE
+}
+
+__global__ __launch_bounds__(kTile) void demod_bank_audio_kernel(const DemodLaunch *__restrict__ recs) {
+    const DemodLaunch a = recs[blockIdx.y];
+    // uniform over the block (a and blockIdx only): no lane is left at a barrier
+    if (a.kind == kKindOff || (long long)blockIdx.x * kTile >= a.n_audio) return;
+#define DEMOD_TILE blockIdx.x
+#include "demod_audio_tile.inc"
+#undef DEMOD_TILE
 }
 
 // ---------------------------------------------------------------- host design
@@ -452,16 +322,15 @@ long long fir_outputs(int D, long long in_total) {
     return lim > 0 ? (lim + D - 1) / D : 0;
 }
 
-}  // namespace
-
-struct rfa_demod {
-    int device = 0;
+// One Demodulator + AudioSink as the host sees it: settings, designed taps and the
+// filters' counters.  An rfa_demod is one of these with its device memory; a bank slot
+// is one of these inside an rfa_demod_bank.  The plan, the staleness rules, the designs
+// and the launch record below work on this part alone, so both run the same code.
+struct DemodSlot {
     int mode = RFA_DEMOD_OFF;
     int32_t width = 0;
     float volume = 1.0f;
     bool sink_enabled = true;
-    hipStream_t stream = nullptr, own_stream = nullptr;
-    std::string err;
     // userFilter (Demodulator.kt:73,215-240)
     bool uf_valid = false;
     std::vector<float> uf_taps;
@@ -476,6 +345,14 @@ struct rfa_demod {
     // AudioSink.audioFilter1 / audioFilter2
     std::vector<float> a1_taps, a2_taps;
     long long a1_in = 0, a1_out = 0, a2_in = 0, a2_out = 0;
+};
+
+}  // namespace
+
+struct rfa_demod : DemodSlot {
+    int device = 0;
+    hipStream_t stream = nullptr, own_stream = nullptr;
+    std::string err;
     // device
     float *d_state[2] = {nullptr, nullptr};
     int cur = 0;
@@ -490,7 +367,8 @@ struct rfa_demod {
 
 namespace {
 
-int mfail(rfa_demod *d, int code, const std::string &msg) {
+template <class H>   // rfa_demod or rfa_demod_bank
+int mfail(H *d, int code, const std::string &msg) {
     if (d) d->err = msg;
     return code;
 }
@@ -502,10 +380,10 @@ int mfail(rfa_demod *d, int code, const std::string &msg) {
     } while (0)
 
 // Demodulator.kt:217: userFilter == null || cutOffFrequency.toInt() != channelWidth
-bool uf_stale(const rfa_demod *d) { return !d->uf_valid || jtoint((double)d->uf_cutoff) != d->width; }
+bool uf_stale(const DemodSlot *d) { return !d->uf_valid || jtoint((double)d->uf_cutoff) != d->width; }
 
 // Demodulator.kt:321-322 (SSB) and :370 (CW), literally
-bool bp_stale(const rfa_demod *d) {
+bool bp_stale(const DemodSlot *d) {
     if (!d->bp_valid) return true;
     if (d->mode == RFA_DEMOD_USB) return jtoint((double)d->bp_hi) != d->width;
     if (d->mode == RFA_DEMOD_LSB) return jtoint((double)d->bp_lo) != -d->width;
@@ -522,7 +400,7 @@ struct Plan {
     long long bp_in0 = 0, bp_out0 = 0, npre = 0, ny1 = 0, n_audio = 0;
 };
 
-void make_plan(const rfa_demod *d, long long n, long long packet, Plan &p) {
+void make_plan(const DemodSlot *d, long long n, long long packet, Plan &p) {
     p.ps = packet > 0 ? packet : std::max(1LL, n);
     p.K = std::max(1LL, (n + p.ps - 1) / p.ps);
     p.uf_fresh = uf_stale(d);
@@ -556,45 +434,192 @@ int upload_taps(rfa_demod *d, int at, const std::vector<float> &t) {
     return RFA_OK;
 }
 
-int rebuild_user_filter(rfa_demod *d) {
+// The filters a call finds stale, designed on the host; nothing of the slot changes until
+// commit_design.  `why` names the rejection.
+struct Design {
+    bool uf = false, bp = false;
+    std::vector<float> uf_taps, bp_re, bp_im;
+    float bp_lo = 0.0f, bp_hi = 0.0f;
+    int bp_dec = 2;
+};
+
+int design_user_filter(const DemodSlot *d, Design &g, const char *&why) {
     const float rate = (float)kModes[d->mode].rate;
-    std::vector<float> t;
     // createLowPass(1, 1f, rate, width, rate * 0.10f, 60) (Demodulator.kt:219-226)
-    if (!design_low_pass(1.0f, rate, (float)d->width, rate * 0.10f, 60.0f, t))
-        return mfail(d, RFA_ERR_INVALID, "user filter design rejected the width (createLowPass returns null)");
-    if (t.size() > (size_t)kMaxUserTaps) return mfail(d, RFA_ERR_UNSUPPORTED, "user filter longer than the kernel's limit");
-    MHIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_UF_RE, 0, 2 * kMaxUserTaps * sizeof(float), d->stream));
-    const int rc = upload_taps(d, TP_UF, t);
-    if (rc != RFA_OK) return rc;
-    d->uf_taps = std::move(t);
-    d->uf_cutoff = (float)d->width;
-    d->uf_in = 0;
-    d->uf_valid = true;
+    if (!design_low_pass(1.0f, rate, (float)d->width, rate * 0.10f, 60.0f, g.uf_taps)) {
+        why = "user filter design rejected the width (createLowPass returns null)";
+        return RFA_ERR_INVALID;
+    }
+    if (g.uf_taps.size() > (size_t)kMaxUserTaps) {
+        why = "user filter longer than the kernel's limit";
+        return RFA_ERR_UNSUPPORTED;
+    }
+    g.uf = true;
     return RFA_OK;
 }
 
-int rebuild_band_pass(rfa_demod *d) {
+int design_band_pass_filter(const DemodSlot *d, Design &g, const char *&why) {
     const float rate = (float)kModes[d->mode].rate, w = (float)d->width;
     float lo, hi;
     int dec = 2;
     if (d->mode == RFA_DEMOD_USB) lo = 200.0f, hi = w;                 // Demodulator.kt:325-333
     else if (d->mode == RFA_DEMOD_LSB) lo = -w, hi = -200.0f;
     else lo = (float)kCwOffset - w / 2.0f, hi = (float)kCwOffset + w / 2.0f, dec = 1;   // :372-380
-    std::vector<float> re, im;
-    if (!design_band_pass(1.0f, rate, lo, hi, rate * 0.01f, 40.0f, re, im))
-        return mfail(d, RFA_ERR_INVALID, "band-pass design rejected the width (createBandPass returns null)");
-    if (re.size() > (size_t)kMaxBandTaps) return mfail(d, RFA_ERR_UNSUPPORTED, "band-pass filter longer than the kernel's limit");
-    MHIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_BP_RE, 0, 2 * kMaxBandTaps * sizeof(float), d->stream));
-    int rc = upload_taps(d, TP_BPR, re);
-    if (rc == RFA_OK) rc = upload_taps(d, TP_BPI, im);
-    if (rc != RFA_OK) return rc;
-    d->bp_re = std::move(re);
-    d->bp_im = std::move(im);
-    d->bp_lo = lo;
-    d->bp_hi = hi;
-    d->bp_dec = dec;
+    if (!design_band_pass(1.0f, rate, lo, hi, rate * 0.01f, 40.0f, g.bp_re, g.bp_im)) {
+        why = "band-pass design rejected the width (createBandPass returns null)";
+        return RFA_ERR_INVALID;
+    }
+    if (g.bp_re.size() > (size_t)kMaxBandTaps) {
+        why = "band-pass filter longer than the kernel's limit";
+        return RFA_ERR_UNSUPPORTED;
+    }
+    g.bp_lo = lo;
+    g.bp_hi = hi;
+    g.bp_dec = dec;
+    g.bp = true;
+    return RFA_OK;
+}
+
+void commit_user_filter(DemodSlot *d, Design &g) {
+    d->uf_taps = g.uf_taps;
+    d->uf_cutoff = (float)d->width;
+    d->uf_in = 0;
+    d->uf_valid = true;
+}
+
+void commit_band_pass(DemodSlot *d, Design &g) {
+    d->bp_re = g.bp_re;
+    d->bp_im = g.bp_im;
+    d->bp_lo = g.bp_lo;
+    d->bp_hi = g.bp_hi;
+    d->bp_dec = g.bp_dec;
     d->bp_in = d->bp_out = 0;
     d->bp_valid = true;
+}
+
+int rebuild_user_filter(rfa_demod *d) {
+    Design g;
+    const char *why = "";
+    const int st = design_user_filter(d, g, why);
+    if (st != RFA_OK) return mfail(d, st, why);
+    MHIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_UF_RE, 0, 2 * kMaxUserTaps * sizeof(float), d->stream));
+    const int rc = upload_taps(d, TP_UF, g.uf_taps);
+    if (rc != RFA_OK) return rc;
+    commit_user_filter(d, g);
+    return RFA_OK;
+}
+
+int rebuild_band_pass(rfa_demod *d) {
+    Design g;
+    const char *why = "";
+    const int st = design_band_pass_filter(d, g, why);
+    if (st != RFA_OK) return mfail(d, st, why);
+    MHIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_BP_RE, 0, 2 * kMaxBandTaps * sizeof(float), d->stream));
+    int rc = upload_taps(d, TP_BPR, g.bp_re);
+    if (rc == RFA_OK) rc = upload_taps(d, TP_BPI, g.bp_im);
+    if (rc != RFA_OK) return rc;
+    commit_band_pass(d, g);
+    return RFA_OK;
+}
+
+// The launch record of one call from the slot and its plan: everything but the addresses.
+void fill_launch(const DemodSlot *d, const Plan &p, long long n_samples, DemodLaunch &a) {
+    a.n = n_samples;
+    a.ps = p.ps;
+    a.K = p.K;
+    a.kind = p.kind;
+    a.Tu = (int)d->uf_taps.size();
+    a.Tb = p.kind == kKindBand ? (int)d->bp_re.size() : 1;
+    a.T1 = (int)d->a1_taps.size();
+    a.T2 = (int)d->a2_taps.size();
+    a.Db = p.Db;
+    a.offb = p.kind == kKindBand ? (int)fir_off(p.Db) : 0;
+    a.skip = (int)p.skip;
+    a.F = p.F;
+    a.bp_in0 = p.bp_in0;
+    a.bp_out0 = p.bp_out0;
+    a.npre = p.npre;
+    if (p.kind == kKindFm) {
+        // quadratureRate / (2 * PI * maxDeviation).toFloat() (Demodulator.kt:176-177,257)
+        const float dev = (float)d->width * (d->mode == RFA_DEMOD_NFM ? 0.75f : 0.85f);
+        a.qgain = (float)kModes[d->mode].rate / (float)(2 * M_PI * (double)dev);
+    }
+    a.volume = d->volume;
+    a.agc = p.kind != kKindFm;
+    a.sink = p.sink;
+    a.a1_in0 = d->a1_in;
+    a.a1_out0 = d->a1_out;
+    a.ny1 = p.ny1;
+    a.a2_in0 = d->a2_in;
+    a.a2_out0 = d->a2_out;
+    a.n_audio = p.n_audio;
+}
+
+// The counters after a call that was enqueued.
+void advance(DemodSlot *d, const Plan &p, long long n_samples) {
+    d->uf_in += n_samples;
+    if (p.kind == kKindBand) {
+        d->bp_in += p.F;
+        d->bp_out += p.npre;
+    }
+    if (p.sink >= 1) {
+        d->a1_in += p.npre;
+        d->a1_out += p.ny1;
+    }
+    if (p.sink == 2) {
+        d->a2_in += p.ny1;
+        d->a2_out += p.n_audio;
+    }
+}
+
+void forget_filters(DemodSlot *d) {
+    d->uf_valid = d->bp_valid = false;
+    d->uf_in = d->bp_in = d->bp_out = 0;
+    d->a1_in = d->a1_out = d->a2_in = d->a2_out = 0;
+}
+
+// AudioSink.java:94-96: createLowPass(decimation 2 / 4, gain 1, rate 1, cut-off, transition, 30 dB)
+bool design_audio_filters(std::vector<float> &t1, std::vector<float> &t2) {
+    return design_low_pass(1.0f, 1.0f, 0.1f, 0.15f, 30.0f, t1) && design_low_pass(1.0f, 1.0f, 0.1f, 0.1f, 30.0f, t2) &&
+           t1.size() <= (size_t)kMaxAudioTaps && t2.size() <= (size_t)kMaxAudioTaps;
+}
+
+void slot_set_mode(DemodSlot *d, int mode) {
+    d->mode = mode;                       // Demodulator.kt:96-100
+    d->width = kModes[mode].def_w;
+}
+
+void slot_set_width(DemodSlot *d, int32_t w) {
+    const ModeInfo &m = kModes[d->mode];  // Demodulator.kt:75
+    d->width = std::min(std::max(w, m.min_w), m.max_w);
+}
+
+int slot_get_taps(const DemodSlot *d, int which, float *re, float *im, size_t capacity, int32_t *num_taps,
+                  int32_t *decimation) {
+    static const std::vector<float> none;
+    const std::vector<float> *r = &none, *i = nullptr;
+    int dec = 1;
+    switch (which) {
+    case RFA_DEMOD_TAPS_USER:
+        if (d->uf_valid) r = &d->uf_taps;
+        break;
+    case RFA_DEMOD_TAPS_BANDPASS:
+        if (d->bp_valid) r = &d->bp_re, i = &d->bp_im, dec = d->bp_dec;
+        break;
+    case RFA_DEMOD_TAPS_AUDIO1: r = &d->a1_taps, dec = kA1Dec; break;
+    case RFA_DEMOD_TAPS_AUDIO2: r = &d->a2_taps, dec = kA2Dec; break;
+    default: return RFA_ERR_INVALID;
+    }
+    if (num_taps) *num_taps = (int32_t)r->size();
+    if (decimation) *decimation = dec;
+    if (re || im) {
+        if (capacity < r->size()) return RFA_ERR_SIZE;
+        if (re) std::memcpy(re, r->data(), r->size() * sizeof(float));
+        if (im) {
+            if (i) std::memcpy(im, i->data(), i->size() * sizeof(float));
+            else std::memset(im, 0, r->size() * sizeof(float));
+        }
+    }
     return RFA_OK;
 }
 
@@ -602,13 +627,12 @@ int rebuild_band_pass(rfa_demod *d) {
 // carry-over and lastMax, audio filters with empty delay lines.
 int fresh_state(rfa_demod *d) {
     MHIP(d, hipMemsetAsync(d->d_state[d->cur], 0, ST_SIZE * sizeof(float), d->stream));
-    d->uf_valid = d->bp_valid = false;
-    d->uf_in = d->bp_in = d->bp_out = 0;
-    d->a1_in = d->a1_out = d->a2_in = d->a2_out = 0;
+    forget_filters(d);
     return RFA_OK;
 }
 
-int grow(rfa_demod *d, float *&p, size_t &cap, size_t want, const char *what) {
+template <class H>
+int grow(H *d, float *&p, size_t &cap, size_t want, const char *what) {
     if (want <= cap) return RFA_OK;
     MHIP(d, hipStreamSynchronize(d->stream));
     if (p) (void)hipFree(p);
@@ -664,10 +688,7 @@ int rfa_demod_create(int device, int mode, rfa_demod **out) {
     d->width = kModes[mode].def_w;
     int rc = RFA_OK;
     std::vector<float> t1, t2;
-    // AudioSink.java:94-96: createLowPass(decimation 2 / 4, gain 1, rate 1, cut-off, transition, 30 dB)
-    if (!design_low_pass(1.0f, 1.0f, 0.1f, 0.15f, 30.0f, t1) || !design_low_pass(1.0f, 1.0f, 0.1f, 0.1f, 30.0f, t2) ||
-        t1.size() > (size_t)kMaxAudioTaps || t2.size() > (size_t)kMaxAudioTaps)
-        rc = RFA_ERR_INVALID;
+    if (!design_audio_filters(t1, t2)) rc = RFA_ERR_INVALID;
     if (rc == RFA_OK && (hipSetDevice(device) != hipSuccess ||
                          hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess))
         rc = RFA_ERR_HIP;
@@ -710,8 +731,7 @@ const char *rfa_demod_last_error(const rfa_demod *d) { return d ? d->err.c_str()
 int rfa_demod_set_mode(rfa_demod *d, int mode) {
     if (!d) return RFA_ERR_INVALID;
     if (!mode_ok(mode)) return mfail(d, RFA_ERR_INVALID, "no such demodulation mode");
-    d->mode = mode;                       // Demodulator.kt:96-100
-    d->width = kModes[mode].def_w;
+    slot_set_mode(d, mode);
     return RFA_OK;
 }
 
@@ -723,8 +743,7 @@ int rfa_demod_get_mode(const rfa_demod *d, int32_t *mode) {
 
 int rfa_demod_set_channel_width(rfa_demod *d, int32_t w) {
     if (!d) return RFA_ERR_INVALID;
-    const ModeInfo &m = kModes[d->mode];  // Demodulator.kt:75
-    d->width = std::min(std::max(w, m.min_w), m.max_w);
+    slot_set_width(d, w);
     return RFA_OK;
 }
 
@@ -779,40 +798,12 @@ int rfa_demod_process(rfa_demod *d, const float *re, const float *im, size_t n_s
     if (rc != RFA_OK) return rc;
 
     DemodLaunch a{};
+    fill_launch(d, p, (long long)n_samples, a);
     a.re = re;
     a.im = im;
-    a.n = (long long)n_samples;
-    a.ps = p.ps;
-    a.K = p.K;
     a.st = d->d_state[d->cur];
     a.nst = d->d_state[d->cur ^ 1];
     a.taps = d->d_taps;
-    a.kind = p.kind;
-    a.Tu = (int)d->uf_taps.size();
-    a.Tb = p.kind == kKindBand ? (int)d->bp_re.size() : 1;
-    a.T1 = (int)d->a1_taps.size();
-    a.T2 = (int)d->a2_taps.size();
-    a.Db = p.Db;
-    a.offb = p.kind == kKindBand ? (int)fir_off(p.Db) : 0;
-    a.skip = (int)p.skip;
-    a.F = p.F;
-    a.bp_in0 = p.bp_in0;
-    a.bp_out0 = p.bp_out0;
-    a.npre = p.npre;
-    if (p.kind == kKindFm) {
-        // quadratureRate / (2 * PI * maxDeviation).toFloat() (Demodulator.kt:176-177,257)
-        const float dev = (float)d->width * (d->mode == RFA_DEMOD_NFM ? 0.75f : 0.85f);
-        a.qgain = (float)kModes[d->mode].rate / (float)(2 * M_PI * (double)dev);
-    }
-    a.volume = d->volume;
-    a.agc = p.kind != kKindFm;
-    a.sink = p.sink;
-    a.a1_in0 = d->a1_in;
-    a.a1_out0 = d->a1_out;
-    a.ny1 = p.ny1;
-    a.a2_in0 = d->a2_in;
-    a.a2_out0 = d->a2_out;
-    a.n_audio = p.n_audio;
     a.pre = d->d_pre;
     a.pk_max = d->d_pk;
     a.pk_avg = d->d_pk + p.K;
@@ -836,19 +827,7 @@ int rfa_demod_process(rfa_demod *d, const float *re, const float *im, size_t n_s
         MHIP(d, hipGetLastError());
     }
     d->cur ^= 1;
-    d->uf_in += (long long)n_samples;
-    if (p.kind == kKindBand) {
-        d->bp_in += p.F;
-        d->bp_out += p.npre;
-    }
-    if (p.sink >= 1) {
-        d->a1_in += p.npre;
-        d->a1_out += p.ny1;
-    }
-    if (p.sink == 2) {
-        d->a2_in += p.ny1;
-        d->a2_out += p.n_audio;
-    }
+    advance(d, p, (long long)n_samples);
     *n_audio = (size_t)p.n_audio;
     return RFA_OK;
 }
@@ -883,31 +862,7 @@ int rfa_demod_process_host(rfa_demod *d, const float *re, const float *im, size_
 int rfa_demod_get_taps(const rfa_demod *d, int which, float *re, float *im, size_t capacity, int32_t *num_taps,
                        int32_t *decimation) {
     if (!d) return RFA_ERR_INVALID;
-    static const std::vector<float> none;
-    const std::vector<float> *r = &none, *i = nullptr;
-    int dec = 1;
-    switch (which) {
-    case RFA_DEMOD_TAPS_USER:
-        if (d->uf_valid) r = &d->uf_taps;
-        break;
-    case RFA_DEMOD_TAPS_BANDPASS:
-        if (d->bp_valid) r = &d->bp_re, i = &d->bp_im, dec = d->bp_dec;
-        break;
-    case RFA_DEMOD_TAPS_AUDIO1: r = &d->a1_taps, dec = kA1Dec; break;
-    case RFA_DEMOD_TAPS_AUDIO2: r = &d->a2_taps, dec = kA2Dec; break;
-    default: return RFA_ERR_INVALID;
-    }
-    if (num_taps) *num_taps = (int32_t)r->size();
-    if (decimation) *decimation = dec;
-    if (re || im) {
-        if (capacity < r->size()) return RFA_ERR_SIZE;
-        if (re) std::memcpy(re, r->data(), r->size() * sizeof(float));
-        if (im) {
-            if (i) std::memcpy(im, i->data(), i->size() * sizeof(float));
-            else std::memset(im, 0, r->size() * sizeof(float));
-        }
-    }
-    return RFA_OK;
+    return slot_get_taps(d, which, re, im, capacity, num_taps, decimation);
 }
 
 int rfa_demod_get_state(rfa_demod *d, float *last_max, float *carry_re, float *carry_im) {
@@ -948,6 +903,418 @@ int rfa_demod_synchronize(rfa_demod *d) {
     if (!d) return RFA_ERR_INVALID;
     MHIP(d, hipSetDevice(d->device));
     MHIP(d, hipStreamSynchronize(d->stream));
+    return RFA_OK;
+}
+
+}  // extern "C"
+
+// ================================================================ the demodulator bank
+//
+// K DemodSlots in one handle: one stream, one set of launches per call.  Slot k's state,
+// taps and scratch are row k of a slab; a call fills one DemodLaunch per slot with the code
+// the single handle uses (make_plan, fill_launch), copies the K records to the device and
+// launches the four bank kernels over (tiles, K).
+//
+// The records of a call are staged in pinned host memory, in a ring of kRecRing entries of
+// K records, each entry with an event recorded behind its copy.  A call waits for the
+// event of the entry it is about to overwrite, so a queued copy never reads records of a
+// later call; the device array is one, because copy and kernels are ordered on the stream.
+
+constexpr int kRecRing = 8;
+
+struct rfa_demod_bank {
+    int device = 0;
+    int K = 0;
+    hipStream_t stream = nullptr, own_stream = nullptr;
+    std::string err;
+    std::vector<DemodSlot> slots;
+    std::vector<int> cur;              // which copy of slot k's state is current
+    std::vector<Plan> plans;           // per call, kept to allocate nothing in steady state
+    float *d_state = nullptr;          // [K][2][ST_SIZE]
+    float *d_taps = nullptr;           // [K][TP_SIZE]
+    float *d_pre = nullptr;            // [K][pre_cap / K]
+    size_t pre_cap = 0;
+    float *d_pk = nullptr;             // [K][pk_cap / K]: max | avg | gain of the slot's packets
+    size_t pk_cap = 0;
+    DemodLaunch *d_recs = nullptr;     // [K]
+    DemodLaunch *h_recs = nullptr;     // pinned, [kRecRing][K]
+    hipEvent_t ev[kRecRing] = {};
+    bool ev_used[kRecRing] = {};
+    int ring_at = 0;
+    float *d_in = nullptr, *d_out = nullptr;   // staging of the _host entry
+    size_t d_in_cap = 0, d_out_cap = 0;
+};
+
+namespace {
+
+float *bank_state(const rfa_demod_bank *b, int k, int which) {
+    return b->d_state + ((size_t)k * 2 + (size_t)which) * ST_SIZE;
+}
+
+bool slot_ok(const rfa_demod_bank *b, int32_t k) { return k >= 0 && k < b->K; }
+
+// What every slot that is not off would do with n samples.
+void bank_plan(rfa_demod_bank *b, long long n, long long packet) {
+    for (int k = 0; k < b->K; k++) {
+        b->plans[k] = Plan{};
+        if (b->slots[k].mode != RFA_DEMOD_OFF) make_plan(&b->slots[k], n, packet, b->plans[k]);
+    }
+}
+
+// Every stale filter of the call: designed first (a rejection leaves all slots as they
+// were), then the delay lines zeroed and the taps uploaded behind one synchronisation.
+int bank_rebuild(rfa_demod_bank *b) {
+    std::vector<std::pair<int, Design>> todo;
+    for (int k = 0; k < b->K; k++) {
+        const DemodSlot *s = &b->slots[k];
+        const Plan &p = b->plans[k];
+        if (s->mode == RFA_DEMOD_OFF || (!p.uf_fresh && !p.bp_fresh)) continue;
+        todo.emplace_back(k, Design{});
+        Design &g = todo.back().second;
+        const char *why = "";
+        int st = RFA_OK;
+        if (p.uf_fresh) st = design_user_filter(s, g, why);
+        if (st == RFA_OK && p.bp_fresh) st = design_band_pass_filter(s, g, why);
+        if (st != RFA_OK) return mfail(b, st, "slot " + std::to_string(k) + ": " + why);
+    }
+    if (todo.empty()) return RFA_OK;
+    for (auto &[k, g] : todo) {
+        float *st = bank_state(b, k, b->cur[k]), *tp = b->d_taps + (size_t)k * TP_SIZE;
+        if (g.uf) {
+            MHIP(b, hipMemsetAsync(st + ST_UF_RE, 0, 2 * kMaxUserTaps * sizeof(float), b->stream));
+            MHIP(b, hipMemcpyAsync(tp + TP_UF, g.uf_taps.data(), g.uf_taps.size() * sizeof(float),
+                                   hipMemcpyHostToDevice, b->stream));
+        }
+        if (g.bp) {
+            MHIP(b, hipMemsetAsync(st + ST_BP_RE, 0, 2 * kMaxBandTaps * sizeof(float), b->stream));
+            MHIP(b, hipMemcpyAsync(tp + TP_BPR, g.bp_re.data(), g.bp_re.size() * sizeof(float), hipMemcpyHostToDevice,
+                                   b->stream));
+            MHIP(b, hipMemcpyAsync(tp + TP_BPI, g.bp_im.data(), g.bp_im.size() * sizeof(float), hipMemcpyHostToDevice,
+                                   b->stream));
+        }
+    }
+    MHIP(b, hipStreamSynchronize(b->stream));             // the designs' host copies are read by now
+    for (auto &[k, g] : todo) {
+        if (g.uf) commit_user_filter(&b->slots[k], g);
+        if (g.bp) commit_band_pass(&b->slots[k], g);
+    }
+    return RFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rfa_demod_bank_create(int device, const int32_t *modes, int32_t n_channels, rfa_demod_bank **out) {
+    if (!out) return RFA_ERR_INVALID;
+    *out = nullptr;
+    if (!modes || n_channels < 1 || n_channels > RFA_DEMOD_BANK_MAX_CHANNELS) return RFA_ERR_INVALID;
+    for (int32_t k = 0; k < n_channels; k++)
+        if (!mode_ok(modes[k])) return RFA_ERR_INVALID;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
+    if (device < 0 || device >= count) return RFA_ERR_INVALID;
+    rfa_demod_bank *b = new (std::nothrow) rfa_demod_bank();
+    if (!b) return RFA_ERR_NOMEM;
+    const size_t K = (size_t)n_channels;
+    b->device = device;
+    b->K = n_channels;
+    int rc = RFA_OK;
+    std::vector<float> t1, t2;
+    if (!design_audio_filters(t1, t2)) rc = RFA_ERR_INVALID;
+    b->slots.resize(K);
+    b->cur.assign(K, 0);
+    b->plans.resize(K);
+    for (size_t k = 0; k < K; k++) {
+        slot_set_mode(&b->slots[k], modes[k]);
+        b->slots[k].a1_taps = t1;
+        b->slots[k].a2_taps = t2;
+    }
+    if (rc == RFA_OK && (hipSetDevice(device) != hipSuccess ||
+                         hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess))
+        rc = RFA_ERR_HIP;
+    if (rc == RFA_OK) {
+        if (hipMalloc(&b->d_state, K * 2 * ST_SIZE * sizeof(float)) != hipSuccess ||
+            hipMalloc(&b->d_taps, K * TP_SIZE * sizeof(float)) != hipSuccess ||
+            hipMalloc(&b->d_recs, K * sizeof(DemodLaunch)) != hipSuccess ||
+            hipHostMalloc(&b->h_recs, (size_t)kRecRing * K * sizeof(DemodLaunch), hipHostMallocDefault) != hipSuccess)
+            rc = RFA_ERR_NOMEM;
+    }
+    for (int e = 0; rc == RFA_OK && e < kRecRing; e++)
+        if (hipEventCreateWithFlags(&b->ev[e], hipEventDisableTiming) != hipSuccess) rc = RFA_ERR_HIP;
+    // fresh Demodulators: zero state; the audio filters' taps in every slot's row
+    std::vector<float> rows;
+    if (rc == RFA_OK) {
+        rows.assign(K * TP_SIZE, 0.0f);
+        for (size_t k = 0; k < K; k++) {
+            std::copy(t1.begin(), t1.end(), rows.begin() + k * TP_SIZE + TP_A1);
+            std::copy(t2.begin(), t2.end(), rows.begin() + k * TP_SIZE + TP_A2);
+        }
+        if (hipMemsetAsync(b->d_state, 0, K * 2 * ST_SIZE * sizeof(float), b->stream) != hipSuccess ||
+            hipMemcpyAsync(b->d_taps, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, b->stream) !=
+                hipSuccess ||
+            hipStreamSynchronize(b->stream) != hipSuccess)
+            rc = RFA_ERR_HIP;
+    }
+    if (rc != RFA_OK) {
+        rfa_demod_bank_destroy(b);
+        return rc;
+    }
+    *out = b;
+    return RFA_OK;
+}
+
+int rfa_demod_bank_destroy(rfa_demod_bank *b) {
+    if (!b) return RFA_ERR_INVALID;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    for (float *p : {b->d_state, b->d_taps, b->d_pre, b->d_pk, b->d_in, b->d_out})
+        if (p) (void)hipFree(p);
+    if (b->d_recs) (void)hipFree(b->d_recs);
+    if (b->h_recs) (void)hipHostFree(b->h_recs);
+    for (hipEvent_t e : b->ev)
+        if (e) (void)hipEventDestroy(e);
+    hipStream_t own = b->own_stream ? b->own_stream : b->stream;
+    if (own) (void)hipStreamDestroy(own);
+    delete b;
+    return RFA_OK;
+}
+
+const char *rfa_demod_bank_last_error(const rfa_demod_bank *b) { return b ? b->err.c_str() : "null handle"; }
+
+int rfa_demod_bank_get_channels(const rfa_demod_bank *b, int32_t *n_channels) {
+    if (!b || !n_channels) return RFA_ERR_INVALID;
+    *n_channels = b->K;
+    return RFA_OK;
+}
+
+int rfa_demod_bank_set_mode(rfa_demod_bank *b, int32_t k, int mode) {
+    if (!b) return RFA_ERR_INVALID;
+    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    if (!mode_ok(mode)) return mfail(b, RFA_ERR_INVALID, "no such demodulation mode");
+    slot_set_mode(&b->slots[k], mode);
+    return RFA_OK;
+}
+
+int rfa_demod_bank_get_mode(const rfa_demod_bank *b, int32_t k, int32_t *mode) {
+    if (!b || !mode || !slot_ok(b, k)) return RFA_ERR_INVALID;
+    *mode = b->slots[k].mode;
+    return RFA_OK;
+}
+
+int rfa_demod_bank_set_channel_width(rfa_demod_bank *b, int32_t k, int32_t w) {
+    if (!b) return RFA_ERR_INVALID;
+    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    slot_set_width(&b->slots[k], w);
+    return RFA_OK;
+}
+
+int rfa_demod_bank_get_channel_width(const rfa_demod_bank *b, int32_t k, int32_t *w) {
+    if (!b || !w || !slot_ok(b, k)) return RFA_ERR_INVALID;
+    *w = b->slots[k].width;
+    return RFA_OK;
+}
+
+int rfa_demod_bank_set_volume(rfa_demod_bank *b, int32_t k, float v) {
+    if (!b) return RFA_ERR_INVALID;
+    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    b->slots[k].volume = v;
+    return RFA_OK;
+}
+
+int rfa_demod_bank_set_audio_sink(rfa_demod_bank *b, int32_t k, int enable) {
+    if (!b) return RFA_ERR_INVALID;
+    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    b->slots[k].sink_enabled = enable != 0;
+    return RFA_OK;
+}
+
+int rfa_demod_bank_get_taps(const rfa_demod_bank *b, int32_t k, int which, float *re, float *im, size_t capacity,
+                            int32_t *num_taps, int32_t *decimation) {
+    if (!b || !slot_ok(b, k)) return RFA_ERR_INVALID;
+    return slot_get_taps(&b->slots[k], which, re, im, capacity, num_taps, decimation);
+}
+
+int rfa_demod_bank_get_state(rfa_demod_bank *b, int32_t k, float *last_max, float *carry_re, float *carry_im) {
+    if (!b) return RFA_ERR_INVALID;
+    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    MHIP(b, hipSetDevice(b->device));
+    float s[3] = {0.0f, 0.0f, 0.0f};
+    MHIP(b, hipMemcpyAsync(s, bank_state(b, k, b->cur[k]) + ST_CARRY, sizeof s, hipMemcpyDeviceToHost, b->stream));
+    MHIP(b, hipStreamSynchronize(b->stream));
+    if (carry_re) *carry_re = s[0];
+    if (carry_im) *carry_im = s[1];
+    if (last_max) *last_max = s[2];
+    return RFA_OK;
+}
+
+int rfa_demod_bank_reset(rfa_demod_bank *b, int32_t k) {
+    if (!b) return RFA_ERR_INVALID;
+    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    MHIP(b, hipSetDevice(b->device));
+    MHIP(b, hipMemsetAsync(bank_state(b, k, b->cur[k]), 0, ST_SIZE * sizeof(float), b->stream));
+    forget_filters(&b->slots[k]);
+    return RFA_OK;
+}
+
+int rfa_demod_bank_max_outputs(const rfa_demod_bank *b, size_t n_samples, size_t *n) {
+    if (!b || !n) return RFA_ERR_INVALID;
+    for (int k = 0; k < b->K; k++) n[k] = 0;
+    if (n_samples > (size_t)1 << 36) return RFA_ERR_INVALID;
+    for (int k = 0; k < b->K; k++) {
+        if (b->slots[k].mode == RFA_DEMOD_OFF) continue;
+        Plan p;
+        make_plan(&b->slots[k], (long long)n_samples, 0, p);
+        n[k] = (size_t)p.n_audio;
+    }
+    return RFA_OK;
+}
+
+int rfa_demod_bank_process(rfa_demod_bank *b, const float *re, const float *im, size_t channel_stride,
+                           size_t n_samples, size_t packet_samples, float *audio, size_t audio_stride,
+                           size_t *n_audio) {
+    if (!b || !n_audio) return RFA_ERR_INVALID;
+    const int K = b->K;
+    for (int k = 0; k < K; k++) n_audio[k] = 0;
+    if (n_samples > (size_t)1 << 36 || packet_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40 ||
+        audio_stride > (size_t)1 << 40)
+        return mfail(b, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return mfail(b, RFA_ERR_INVALID, "null input");
+    if (K > 1 && channel_stride < n_samples) return mfail(b, RFA_ERR_INVALID, "channel_stride below n_samples");
+    bank_plan(b, (long long)n_samples, (long long)packet_samples);
+    long long max_npre = 0, max_audio = 0, max_pk = 0;
+    bool any_on = false, any_agc = false;
+    for (int k = 0; k < K; k++) {
+        if (b->slots[k].mode == RFA_DEMOD_OFF) continue;     // Demodulator.kt:174: no output, nothing moves
+        const Plan &p = b->plans[k];
+        any_on = true;
+        any_agc = any_agc || p.kind != kKindFm;
+        max_npre = std::max(max_npre, p.npre);
+        max_audio = std::max(max_audio, p.n_audio);
+        max_pk = std::max(max_pk, p.K);
+    }
+    if ((size_t)max_audio > audio_stride) return mfail(b, RFA_ERR_SIZE, "audio_stride too small for a slot");
+    if (max_audio > 0 && !audio) return mfail(b, RFA_ERR_INVALID, "null output");
+    if (max_pk > (long long)INT32_MAX || (max_npre + kTile - 1) / kTile > (long long)INT32_MAX)
+        return mfail(b, RFA_ERR_INVALID, "call too large for one grid");
+    if (!any_on) return RFA_OK;
+    MHIP(b, hipSetDevice(b->device));
+    int rc = grow(b, b->d_pre, b->pre_cap, (size_t)K * (size_t)max_npre, "scratch");
+    if (rc == RFA_OK) rc = grow(b, b->d_pk, b->pk_cap, (size_t)K * 3 * (size_t)max_pk, "packet scratch");
+    if (rc == RFA_OK) rc = bank_rebuild(b);
+    if (rc != RFA_OK) return rc;
+
+    // this call's records: wait until the ring entry's previous copy has been made
+    const int e = b->ring_at;
+    if (b->ev_used[e]) MHIP(b, hipEventSynchronize(b->ev[e]));
+    DemodLaunch *recs = b->h_recs + (size_t)e * (size_t)K;
+    const size_t pre_row = b->pre_cap / (size_t)K, pk_row = b->pk_cap / (size_t)K;
+    for (int k = 0; k < K; k++) {
+        DemodLaunch a{};
+        a.kind = kKindOff;
+        if (b->slots[k].mode != RFA_DEMOD_OFF) {
+            const Plan &p = b->plans[k];
+            fill_launch(&b->slots[k], p, (long long)n_samples, a);
+            a.re = re + (size_t)k * channel_stride;
+            a.im = im + (size_t)k * channel_stride;
+            a.st = bank_state(b, k, b->cur[k]);
+            a.nst = bank_state(b, k, b->cur[k] ^ 1);
+            a.taps = b->d_taps + (size_t)k * TP_SIZE;
+            a.pre = b->d_pre + (size_t)k * pre_row;
+            a.pk_max = b->d_pk + (size_t)k * pk_row;
+            a.pk_avg = a.pk_max + p.K;
+            a.pk_gain = a.pk_max + 2 * p.K;
+            a.out = audio + (size_t)k * audio_stride;
+        }
+        recs[k] = a;
+    }
+    MHIP(b, hipMemcpyAsync(b->d_recs, recs, (size_t)K * sizeof(DemodLaunch), hipMemcpyHostToDevice, b->stream));
+    MHIP(b, hipEventRecord(b->ev[e], b->stream));
+    b->ev_used[e] = true;
+    b->ring_at = (e + 1) % kRecRing;
+
+    if (max_npre > 0) {
+        hipLaunchKernelGGL(demod_bank_stage1_kernel, dim3((unsigned)((max_npre + kTile - 1) / kTile), (unsigned)K),
+                           dim3(kTile), 0, b->stream, b->d_recs);
+        MHIP(b, hipGetLastError());
+    }
+    if (any_agc) {
+        hipLaunchKernelGGL(demod_bank_packet_kernel, dim3((unsigned)max_pk, (unsigned)K), dim3(64), 0, b->stream,
+                           b->d_recs);
+        MHIP(b, hipGetLastError());
+    }
+    hipLaunchKernelGGL(demod_bank_state_kernel, dim3((unsigned)K), dim3(kTile), 0, b->stream, b->d_recs);
+    MHIP(b, hipGetLastError());
+    if (max_audio > 0) {
+        hipLaunchKernelGGL(demod_bank_audio_kernel, dim3((unsigned)((max_audio + kTile - 1) / kTile), (unsigned)K),
+                           dim3(kTile), 0, b->stream, b->d_recs);
+        MHIP(b, hipGetLastError());
+    }
+    for (int k = 0; k < K; k++) {
+        if (b->slots[k].mode == RFA_DEMOD_OFF) continue;
+        b->cur[k] ^= 1;
+        advance(&b->slots[k], b->plans[k], (long long)n_samples);
+        n_audio[k] = (size_t)b->plans[k].n_audio;
+    }
+    return RFA_OK;
+}
+
+int rfa_demod_bank_process_host(rfa_demod_bank *b, const float *re, const float *im, size_t channel_stride,
+                                size_t n_samples, size_t packet_samples, float *audio, size_t audio_stride,
+                                size_t *n_audio) {
+    if (!b || !n_audio) return RFA_ERR_INVALID;
+    const size_t K = (size_t)b->K;
+    for (size_t k = 0; k < K; k++) n_audio[k] = 0;
+    if (n_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40 || audio_stride > (size_t)1 << 40)
+        return mfail(b, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return mfail(b, RFA_ERR_INVALID, "null input");
+    if (K > 1 && channel_stride < n_samples) return mfail(b, RFA_ERR_INVALID, "channel_stride below n_samples");
+    bank_plan(b, (long long)n_samples, (long long)packet_samples);
+    size_t max_audio = 0;
+    for (size_t k = 0; k < K; k++)
+        if (b->slots[k].mode != RFA_DEMOD_OFF) max_audio = std::max(max_audio, (size_t)b->plans[k].n_audio);
+    if (max_audio > audio_stride) return mfail(b, RFA_ERR_SIZE, "audio_stride too small for a slot");
+    if (max_audio > 0 && !audio) return mfail(b, RFA_ERR_INVALID, "null output");
+    MHIP(b, hipSetDevice(b->device));
+    int rc = grow(b, b->d_in, b->d_in_cap, 2 * K * n_samples, "input staging");
+    if (rc == RFA_OK) rc = grow(b, b->d_out, b->d_out_cap, K * max_audio, "output staging");
+    if (rc != RFA_OK) return rc;
+    float *d_re = b->d_in, *d_im = b->d_in + K * n_samples;
+    if (n_samples) {
+        const size_t row = n_samples * sizeof(float), pitch = (K > 1 ? channel_stride : n_samples) * sizeof(float);
+        MHIP(b, hipMemcpy2DAsync(d_re, row, re, pitch, row, K, hipMemcpyHostToDevice, b->stream));
+        MHIP(b, hipMemcpy2DAsync(d_im, row, im, pitch, row, K, hipMemcpyHostToDevice, b->stream));
+    }
+    rc = rfa_demod_bank_process(b, d_re, d_im, n_samples, n_samples, packet_samples, b->d_out, max_audio, n_audio);
+    if (rc != RFA_OK) return rc;
+    for (size_t k = 0; k < K; k++)      // a slot's row of the caller's buffer is written up to its own count
+        if (n_audio[k])
+            MHIP(b, hipMemcpyAsync(audio + k * audio_stride, b->d_out + k * max_audio, n_audio[k] * sizeof(float),
+                                   hipMemcpyDeviceToHost, b->stream));
+    MHIP(b, hipStreamSynchronize(b->stream));
+    return RFA_OK;
+}
+
+int rfa_demod_bank_set_stream(rfa_demod_bank *b, void *stream) {
+    if (!b) return RFA_ERR_INVALID;
+    // the carried state and the record ring are ordered on the bank's stream: drain it first
+    MHIP(b, hipSetDevice(b->device));
+    MHIP(b, hipStreamSynchronize(b->stream));
+    if (b->own_stream == nullptr) b->own_stream = b->stream;
+    b->stream = stream ? (hipStream_t)stream : b->own_stream;
+    return RFA_OK;
+}
+
+int rfa_demod_bank_get_stream(const rfa_demod_bank *b, void **stream) {
+    if (!b || !stream) return RFA_ERR_INVALID;
+    *stream = (void *)b->stream;
+    return RFA_OK;
+}
+
+int rfa_demod_bank_synchronize(rfa_demod_bank *b) {
+    if (!b) return RFA_ERR_INVALID;
+    MHIP(b, hipSetDevice(b->device));
+    MHIP(b, hipStreamSynchronize(b->stream));
     return RFA_OK;
 }
 

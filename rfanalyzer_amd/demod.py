@@ -25,7 +25,9 @@ to 48 kHz audio through ``rfa_demod_*`` (``rfanalyzer_amd/csrc/demod.hip``) -- a
 
 ``FrontEndBank`` is K front ends on one raw stream in two launches per call
 (``rfa_ddc_bank_*``): one filter, a mixer and a delay line per slot, each slot bit for bit a
-``FrontEnd``; ``ReceiverBank`` feeds one ``Demodulator`` per slot from it.
+``FrontEnd``.  ``DemodulatorBank`` is K demodulators in four launches per call
+(``rfa_demod_bank_*``), each slot bit for bit a ``Demodulator``; ``ReceiverBank`` chains the
+two banks.
 """
 from __future__ import annotations
 
@@ -599,6 +601,172 @@ class Demodulator:
         return s.value or 0
 
 
+class DemodulatorBank:
+    """``len(modes)`` demodulators, each with its AudioSink, in one handle (``rfa_demod_bank_*``):
+    one stream and one set of launches -- four kernels and one copy of the slots' launch
+    records per call, whatever the slot count.  Slot k gives bit for bit what a ``Demodulator``
+    with the same settings and calls gives; the per-slot methods behave as its properties do.
+    Modes of different quadrature rates may share a bank; an "off" slot returns no audio and
+    keeps its state."""
+
+    def __init__(self, modes, device: int = 0, audio_sink: bool = True):
+        self._h = None
+        self._stream = None
+        ids = [_mode_id(m) for m in modes]
+        self.n_channels = len(ids)
+        h = _lib._h()
+        arr = (ctypes.c_int32 * max(len(ids), 1))(*ids)
+        _lib.check(_lib.lib().rfa_demod_bank_create(device, arr, len(ids), ctypes.byref(h)), "rfa_demod_bank_create")
+        self._h = h
+        self._counts = (ctypes.c_size_t * self.n_channels)()
+        if not audio_sink:
+            for k in range(self.n_channels):
+                self.set_audio_sink(k, False)
+
+    # -- lifetime
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.lib().rfa_demod_bank_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def _check(self, status: int, where: str) -> None:
+        if status != _lib.RFA_OK:
+            detail = (_lib.lib().rfa_demod_bank_last_error(self._h) or b"").decode()
+            raise _lib.RfaError(status, where, detail)
+
+    # -- per slot, as the Demodulator's properties
+    def mode(self, k: int) -> int:
+        m = ctypes.c_int32(0)
+        self._check(_lib.lib().rfa_demod_bank_get_mode(self._h, k, ctypes.byref(m)), "rfa_demod_bank_get_mode")
+        return m.value
+
+    def set_mode(self, k: int, mode) -> None:
+        self._check(_lib.lib().rfa_demod_bank_set_mode(self._h, k, _mode_id(mode)), "rfa_demod_bank_set_mode")
+
+    def channel_width(self, k: int) -> int:
+        w = ctypes.c_int32(0)
+        self._check(_lib.lib().rfa_demod_bank_get_channel_width(self._h, k, ctypes.byref(w)),
+                    "rfa_demod_bank_get_channel_width")
+        return w.value
+
+    def set_channel_width(self, k: int, width: int) -> None:
+        self._check(_lib.lib().rfa_demod_bank_set_channel_width(self._h, k, int(width)),
+                    "rfa_demod_bank_set_channel_width")
+
+    def set_volume(self, k: int, v: float) -> None:
+        self._check(_lib.lib().rfa_demod_bank_set_volume(self._h, k, float(v)), "rfa_demod_bank_set_volume")
+
+    def set_audio_sink(self, k: int, on: bool) -> None:
+        self._check(_lib.lib().rfa_demod_bank_set_audio_sink(self._h, k, 1 if on else 0),
+                    "rfa_demod_bank_set_audio_sink")
+
+    def taps(self, k: int, which: str):
+        """Slot k's ("user" | "bandpass" | "audio1" | "audio2") -> (re, im, decimation)."""
+        n, d = ctypes.c_int32(0), ctypes.c_int32(0)
+        L = _lib.lib()
+        self._check(L.rfa_demod_bank_get_taps(self._h, k, TAPS[which], None, None, 0, ctypes.byref(n),
+                                              ctypes.byref(d)), "rfa_demod_bank_get_taps")
+        re = np.empty(n.value, np.float32)
+        im = np.empty(n.value, np.float32)
+        self._check(L.rfa_demod_bank_get_taps(self._h, k, TAPS[which], re.ctypes.data_as(_lib._fp),
+                                              im.ctypes.data_as(_lib._fp), re.size, ctypes.byref(n), ctypes.byref(d)),
+                    "rfa_demod_bank_get_taps")
+        return re, im, d.value
+
+    def state(self, k: int):
+        """Slot k's (lastMax, carryOverSamplesRe, carryOverSamplesIm); drains the stream."""
+        v = [ctypes.c_float(0) for _ in range(3)]
+        self._check(_lib.lib().rfa_demod_bank_get_state(self._h, k, *[ctypes.byref(x) for x in v]),
+                    "rfa_demod_bank_get_state")
+        return tuple(np.float32(x.value) for x in v)
+
+    def reset(self, k: int) -> None:
+        self._check(_lib.lib().rfa_demod_bank_reset(self._h, k), "rfa_demod_bank_reset")
+
+    def max_outputs(self, n_samples: int) -> list[int]:
+        """Every slot's audio sample count for the next call of ``n_samples``."""
+        n = (ctypes.c_size_t * self.n_channels)()
+        self._check(_lib.lib().rfa_demod_bank_max_outputs(self._h, n_samples, n), "rfa_demod_bank_max_outputs")
+        return list(n)
+
+    # -- processing
+    def process(self, re, im, packet_samples: int | None = None) -> list[np.ndarray]:
+        """Host planar float32 [K, n] in -> K float32 audio arrays."""
+        re = np.ascontiguousarray(re, np.float32)
+        im = np.ascontiguousarray(im, np.float32)
+        if re.shape != im.shape or re.ndim != 2 or re.shape[0] != self.n_channels:
+            raise ValueError(f"re and im must both have shape [{self.n_channels}, n]")
+        n = re.shape[1]
+        cap = max(self.max_outputs(n))
+        out = np.empty((self.n_channels, max(cap, 1)), np.float32)
+        self._check(_lib.lib().rfa_demod_bank_process_host(self._h, re.ctypes.data, im.ctypes.data, n, n,
+                                                           packet_samples or 0, out.ctypes.data, out.shape[1],
+                                                           self._counts), "rfa_demod_bank_process_host")
+        return [out[k, :g].copy() for k, g in enumerate(self._counts)]
+
+    def process_device(self, re_ptr: int, im_ptr: int, channel_stride: int, n_samples: int, audio_ptr: int,
+                       audio_stride: int, packet_samples: int | None = None) -> list[int]:
+        """Device pointers, rows ``channel_stride`` / ``audio_stride`` floats apart; asynchronous on
+        the bank's stream; returns every slot's audio sample count."""
+        self._check(_lib.lib().rfa_demod_bank_process(self._h, re_ptr, im_ptr, channel_stride, n_samples,
+                                                      packet_samples or 0, audio_ptr, audio_stride, self._counts),
+                    "rfa_demod_bank_process")
+        return list(self._counts)
+
+    def set_stream(self, stream_ptr: int | None) -> None:
+        """Enqueue on exactly this hipStream_t (None: the bank's own stream)."""
+        self._check(_lib.lib().rfa_demod_bank_set_stream(self._h, stream_ptr or None), "rfa_demod_bank_set_stream")
+        self._stream = stream_ptr or None
+
+    def process_tensor(self, re, im, out, packet_samples: int | None = None) -> list[int]:
+        """torch.cuda float32 tensors [K, n] (rows may be slices of wider tensors: unit stride
+        along n) -> ``out`` [K, capacity]; on torch's current stream (see
+        ``Demodulator.process_tensor``)."""
+        import torch
+
+        cur = torch.cuda.current_stream(re.device).cuda_stream
+        if cur != self._stream:
+            self.set_stream(cur)
+        K = self.n_channels
+        if re.shape != im.shape or re.dim() != 2 or re.shape[0] != K or out.dim() != 2 or out.shape[0] != K:
+            raise ValueError(f"re, im and out must have shape [{K}, .]")
+        for t in (re, im, out):
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("rows must be contiguous")
+        if K > 1 and re.stride(0) != im.stride(0):
+            raise ValueError("re and im must have the same row stride")
+        stride = re.stride(0) if K > 1 else re.shape[1]
+        ostride = out.stride(0) if K > 1 else out.shape[1]
+        if K > 1 and ostride < out.shape[1]:
+            raise ValueError("out's rows overlap")
+        if ostride > out.shape[1] and max(self.max_outputs(re.shape[1])) > out.shape[1]:
+            # rows of a wider tensor: the C entry's capacity is the row pitch, the view is narrower
+            raise _lib.RfaError(_lib.RFA_ERR_SIZE, "rfa_demod_bank_process", "out's rows are too short for a slot")
+        return self.process_device(re.data_ptr(), im.data_ptr(), stride, re.shape[1], out.data_ptr(), ostride,
+                                   packet_samples)
+
+    def synchronize(self) -> None:
+        self._check(_lib.lib().rfa_demod_bank_synchronize(self._h), "rfa_demod_bank_synchronize")
+
+    @property
+    def stream(self) -> int:
+        s = _lib._vp()
+        self._check(_lib.lib().rfa_demod_bank_get_stream(self._h, ctypes.byref(s)), "rfa_demod_bank_get_stream")
+        return s.value or 0
+
+
 class Receiver:
     """Raw IQ bytes -> audio: ``FrontEnd(..., resampler=True)`` at the mode's quadrature rate
     chained into a ``Demodulator``, device to device on one stream.  One ``process`` call is
@@ -704,11 +872,11 @@ class Receiver:
 
 class ReceiverBank:
     """Raw IQ bytes -> one audio stream per channel: a ``FrontEndBank(..., resampler=True)`` at
-    the modes' quadrature rate feeding one ``Demodulator`` per slot, device to device on one
-    stream.  Slot k's audio equals, bit for bit, a ``Receiver`` in mode ``modes[k]`` tuned to
-    channel k and given the same packets.  The slots share the resampler, so every mode must
-    have the same quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``).
-    The demodulators are not banked: a packet is 2 + 4 K launches."""
+    the modes' quadrature rate feeding a ``DemodulatorBank``, device to device on one stream.
+    Slot k's audio equals, bit for bit, a ``Receiver`` in mode ``modes[k]`` tuned to channel k
+    and given the same packets.  The slots share the resampler, so every mode must have the
+    same quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``).
+    Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
 
     def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0):
         import torch
@@ -723,11 +891,12 @@ class ReceiverBank:
         self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
         self._tdev = torch.device("cuda", device)
         self.quadrature_rate = rates.pop()
-        self.demods, self.front = [], None
+        self.demods, self.front = None, None
+        self._n_channels = len(modes)
         self._raw = self._re = self._im = self._audio = None
         self._cap_for = (None, 0)
         try:
-            self.demods = [Demodulator(m, device) for m in modes]
+            self.demods = DemodulatorBank(modes, device)
             self.front = FrontEndBank(input_format, self.sample_rate, self.quadrature_rate, len(modes), device,
                                       resampler=True)
             self.set_stream(None)
@@ -737,31 +906,28 @@ class ReceiverBank:
 
     @property
     def n_channels(self) -> int:
-        return len(self.demods)
+        return self._n_channels
 
     def mode(self, k: int) -> int:
-        return self.demods[k].demodulationMode
+        return self.demods.mode(k)
 
     def set_mode(self, k: int, mode) -> None:
         """Slot k's DemodulationMode; only to a mode of the bank's quadrature rate."""
         if mode_info(mode)[0] != self.quadrature_rate:
             raise ValueError(f"mode {mode!r} has quadrature rate {mode_info(mode)[0]}, the bank runs at "
                              f"{self.quadrature_rate}")
-        self.demods[k].demodulationMode = mode
+        self.demods.set_mode(k, mode)
 
     def set_frequencies(self, frequency: int, channel_frequencies) -> None:
         self.front.set_frequencies(frequency, channel_frequencies)
 
     def set_stream(self, stream_ptr: int | None) -> None:
-        """Enqueue every stage on exactly this hipStream_t (None: the first demodulator's own)."""
-        self.demods[0].set_stream(stream_ptr)
-        shared = self.demods[0].stream
-        for d in self.demods[1:]:
-            d.set_stream(shared)
-        self.front.set_stream(shared)
+        """Enqueue every stage on exactly this hipStream_t (None: the demodulator bank's own)."""
+        self.demods.set_stream(stream_ptr)
+        self.front.set_stream(self.demods.stream)
 
     def synchronize(self) -> None:
-        self.demods[0].synchronize()
+        self.demods.synchronize()
 
     def _buffers(self, nbytes: int, n: int) -> int:
         torch = self._torch
@@ -782,9 +948,8 @@ class ReceiverBank:
         asynchronous on the bank's stream; returns every slot's audio sample count."""
         cap = self._buffers(0, n_samples)
         nq = self.front.process_device(raw_ptr, n_samples, self._re.data_ptr(), self._im.data_ptr(), cap)
-        row = 4 * cap
-        return [d.process_device(self._re.data_ptr() + k * row, self._im.data_ptr() + k * row, nq,
-                                 self._audio.data_ptr() + k * row, cap) for k, d in enumerate(self.demods)]
+        return self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq, self._audio.data_ptr(),
+                                          cap)
 
     @property
     def audio_tensor(self):
@@ -810,9 +975,9 @@ class ReceiverBank:
         if self.front is not None:
             self.front.close()
             self.front = None
-        for d in self.demods:
-            d.close()
-        self.demods = []
+        if self.demods is not None:
+            self.demods.close()
+            self.demods = None
 
     def __enter__(self):
         return self

@@ -101,6 +101,67 @@ static void check_handle_errors() {
     CHECK(rfa_demod_synchronize(nullptr) == RFA_ERR_INVALID);
 }
 
+// The bank's device-less paths: every entry on a null handle or with null outputs,
+// and the creation arguments that must be rejected before the device is looked for.
+static void check_bank_errors() {
+    const int32_t ok_modes[3] = {RFA_DEMOD_AM, RFA_DEMOD_NFM, RFA_DEMOD_OFF};
+    const int32_t bad_modes[3] = {RFA_DEMOD_AM, 7, RFA_DEMOD_NFM};
+    const int32_t neg_modes[2] = {RFA_DEMOD_CW, -1};
+    std::vector<int32_t> many(RFA_DEMOD_BANK_MAX_CHANNELS + 1, RFA_DEMOD_NFM);
+    rfa_demod_bank *b = reinterpret_cast<rfa_demod_bank *>(0x1);
+    CHECK(rfa_demod_bank_create(0, ok_modes, 3, nullptr) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_create(0, nullptr, 3, &b) == RFA_ERR_INVALID && b == nullptr);
+    b = reinterpret_cast<rfa_demod_bank *>(0x1);
+    CHECK(rfa_demod_bank_create(0, ok_modes, 0, &b) == RFA_ERR_INVALID && b == nullptr);
+    b = reinterpret_cast<rfa_demod_bank *>(0x1);
+    CHECK(rfa_demod_bank_create(0, ok_modes, -1, &b) == RFA_ERR_INVALID && b == nullptr);
+    b = reinterpret_cast<rfa_demod_bank *>(0x1);
+    CHECK(rfa_demod_bank_create(0, many.data(), RFA_DEMOD_BANK_MAX_CHANNELS + 1, &b) == RFA_ERR_INVALID && b == nullptr);
+    b = reinterpret_cast<rfa_demod_bank *>(0x1);
+    CHECK(rfa_demod_bank_create(0, bad_modes, 3, &b) == RFA_ERR_INVALID && b == nullptr);
+    b = reinterpret_cast<rfa_demod_bank *>(0x1);
+    CHECK(rfa_demod_bank_create(0, neg_modes, 2, &b) == RFA_ERR_INVALID && b == nullptr);
+    // a valid request: the device is looked for only now (this program runs where there is none)
+    b = reinterpret_cast<rfa_demod_bank *>(0x1);
+    const int st = rfa_demod_bank_create(0, many.data(), RFA_DEMOD_BANK_MAX_CHANNELS, &b);
+    CHECK(st == RFA_ERR_NODEVICE || st == RFA_OK);
+    CHECK((st == RFA_OK) == (b != nullptr));
+    if (b) CHECK(rfa_demod_bank_destroy(b) == RFA_OK);
+
+    CHECK(rfa_demod_bank_destroy(nullptr) == RFA_ERR_INVALID);
+    CHECK(std::strcmp(rfa_demod_bank_last_error(nullptr), "null handle") == 0);
+    int32_t w = 0;
+    size_t n[4] = {9, 9, 9, 9};
+    float f = 0;
+    void *s = nullptr;
+    for (int32_t k : {0, -1, 5, RFA_DEMOD_BANK_MAX_CHANNELS}) {      // a slot index, in or out of range, on a null handle
+        CHECK(rfa_demod_bank_set_mode(nullptr, k, RFA_DEMOD_AM) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_get_mode(nullptr, k, &w) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_get_mode(nullptr, k, nullptr) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_set_channel_width(nullptr, k, 1) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_get_channel_width(nullptr, k, &w) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_get_channel_width(nullptr, k, nullptr) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_set_volume(nullptr, k, 1.0f) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_set_audio_sink(nullptr, k, 1) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_get_taps(nullptr, k, 0, nullptr, nullptr, 0, &w, &w) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_get_state(nullptr, k, &f, &f, &f) == RFA_ERR_INVALID);
+        CHECK(rfa_demod_bank_reset(nullptr, k) == RFA_ERR_INVALID);
+    }
+    CHECK(rfa_demod_bank_get_channels(nullptr, &w) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_get_channels(nullptr, nullptr) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_max_outputs(nullptr, 1, n) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_max_outputs(nullptr, 1, nullptr) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_process(nullptr, nullptr, nullptr, 0, 0, 0, nullptr, 0, n) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_process(nullptr, nullptr, nullptr, 0, 0, 0, nullptr, 0, nullptr) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_process_host(nullptr, nullptr, nullptr, 0, 0, 0, nullptr, 0, n) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_process_host(nullptr, nullptr, nullptr, 0, 0, 0, nullptr, 0, nullptr) == RFA_ERR_INVALID);
+    CHECK(n[0] == 9 && n[3] == 9);                                    // nothing written through a null handle
+    CHECK(rfa_demod_bank_set_stream(nullptr, nullptr) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_get_stream(nullptr, &s) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_get_stream(nullptr, nullptr) == RFA_ERR_INVALID);
+    CHECK(rfa_demod_bank_synchronize(nullptr) == RFA_ERR_INVALID);
+}
+
 int main() {
     check_mode_table();
     check_band_pass(96000.0f, 200.0f, 2800.0f);      // USB
@@ -108,6 +169,7 @@ int main() {
     check_band_pass(48000.0f, 600.0f, 900.0f);       // CW
     check_band_pass_errors();
     check_handle_errors();
+    check_bank_errors();
     if (failures) {
         std::fprintf(stderr, "demod_host_check: %d check(s) failed\n", failures);
         return 1;
