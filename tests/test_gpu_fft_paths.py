@@ -47,8 +47,8 @@ import signals
 
 pytestmark = pytest.mark.gpu
 
-BPS = {"s8": 2, "u8": 2, "s16": 4, "f32": 8}
-LOAD_ALIGN = {"s8": 2, "u8": 2, "s16": 4, "f32": 8}  # engine.hip load_alignment()
+BPS = {"s8": 2, "u8": 2, "s16": 4, "f32": 8, "f32p": 8}
+LOAD_ALIGN = {"s8": 2, "u8": 2, "s16": 4, "f32": 8, "f32p": 4}  # engine.hip load_alignment()
 TONES = ((0.173, 0.5), (-0.29, 0.01))                # as test_all_sizes_and_formats_vs_oracle
 NOISE = 0.03
 RFA_ERR_INVALID = -1
@@ -298,6 +298,12 @@ def test_seam_entries_reach_their_kernels(rfa, n):
     /f32/C).  At 8 K / 16 K the same entries stay on the wide kernel's direct f32 / f32p forms
     and its complex-output form fft_wide_kernel<13 | 14, 32, 1, f32, CO>.  Against float64
     (0.01 dB; ordered spectrum 2e-6 relative, test_gpu_seam.py's bar) and the reference pffft."""
+    check_seam_entries(rfa, n)
+
+
+def check_seam_entries(rfa, n):
+    """The three seam entries of one handle of size ``n`` on seam_input(n), against float64 and,
+    where it is built, the reference's pffft (shared with tests/test_gpu_fft_small.py)."""
     x, exact, ref_db, xw, ref_wdb = seam_reference(n)
     with rfa.SpectrumEngine(n, "blackman", "s8", ring_rows=0) as e:
         cx = e.fft_ordered(x)
@@ -306,10 +312,11 @@ def test_seam_entries_reach_their_kernels(rfa, n):
         assert e.windowed_fft_mag(x[0::2].copy(), x[1::2].copy(), wmag)
     g = cx[0::2].astype(np.float64) + 1j * cx[1::2]
     rel = np.abs(g - exact).max() / np.abs(exact).max()
-    print(f"{n}: ordered rel err {rel:.3e}")
+    d_mag, d_wmag = gu.db_diff(mag, ref_db), gu.db_diff(wmag, ref_wdb)
+    print(f"{n}: ordered rel err {rel:.3e}, fft_logmag {d_mag:.3e} dB, windowed_fft_mag {d_wmag:.3e} dB above the floor")
     assert rel < 2e-6
-    assert gu.db_diff(mag, ref_db) <= gu.DB_TOL
-    assert gu.db_diff(wmag, ref_wdb) <= gu.DB_TOL
+    assert d_mag <= gu.DB_TOL
+    assert d_wmag <= gu.DB_TOL
     if oracle.ref_available():
         r = oracle.ref_fft_ordered(x)
         rr = r[0::2].astype(np.float64) + 1j * r[1::2]

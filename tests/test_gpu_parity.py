@@ -260,10 +260,10 @@ def test_reference_seams_match_pffft(rfa):
     dsp.close()
 
 
-@pytest.mark.parametrize("n,frames", [(262144, 65), (1048576, 17)])
+@pytest.mark.parametrize("n,frames", [(262144, 65), (524288, 33), (1048576, 17)])
 def test_large_n_batches_cross_the_scratch_split(rfa, n, frames):
     """N > 2^17 runs as two kernels over batches of 128 MB of scratch
-    (64 frames at 2^18, 16 at 2^20): a batch one frame longer crosses the split;
+    (64 frames at 2^18, 32 at 2^19, 16 at 2^20): a batch one frame longer crosses the split;
     rows, ring and peak-hold must not see the seam."""
     data = signals.frames_bytes(n, frames, "s8", n + 3, tones=((0.2113, 0.4),), noise=0.05, drift=2e-4)
     ref = oracle.spectrum_rows(data, oracle.IN_S8, n, frames, None, oracle.WIN_BLACKMAN)
@@ -277,7 +277,7 @@ def test_large_n_batches_cross_the_scratch_split(rfa, n, frames):
     assert gu.db_diff(peaks, ref.max(0)) <= gu.DB_TOL
 
 
-@pytest.mark.parametrize("n", [262144, 1048576])
+@pytest.mark.parametrize("n", [262144, 524288, 1048576])
 def test_large_n_seams(rfa, n):
     """Reference seams at N > 2^17: ordered complex FFT vs float64, log-mag vs pffft."""
     rng = np.random.default_rng(n)
@@ -295,10 +295,10 @@ def test_large_n_seams(rfa, n):
     dsp.close()
 
 
-@pytest.mark.parametrize("n,frames", [(1 << 20, 7), (1 << 18, 9)])
+@pytest.mark.parametrize("n,frames", [(1 << 20, 7), (1 << 19, 7), (1 << 18, 9)])
 @pytest.mark.parametrize("fmt", ["s8", "u8"])
 def test_large_n_front_kernel_alignment_paths(rfa, fmt, n, frames):
-    """N = 1 M and 256 K, 8-bit input: 16-byte aligned frames go straight to the pipelined persistent
+    """N = 1 M, 512 K and 256 K, 8-bit input: 16-byte aligned frames go straight to the pipelined persistent
     front kernel (LDS-DMA tiles); a misaligned device pointer is first copied 16-B aligned
     (round 5), so the same kernel rounds them and the rows are bit-identical; both match the
     oracle; 7 frames over 6 frame groups exercises the uneven split.  A single misaligned frame
