@@ -560,6 +560,27 @@ RFA_API int rfa_ddc_bank_synchronize(rfa_ddc_bank *b);
  * is the empty table.  RFA_ERR_UNSUPPORTED for RFA_IN_F32_INTERLEAVED. */
 RFA_API int rfa_ddc_mix_info(int input_format, int32_t sample_rate, int64_t frequency, int64_t channel_frequency,
                              int32_t *mix_frequency, int32_t *table_length);
+/* Host only, no handle and no device needed: the workgroup tile plan every
+ * rfa_ddc_process / rfa_ddc_bank_process call of such a filter launches with
+ * (the same planning code the launch runs).  taps_per_output, interpolation and
+ * decimation as rfa_ddc_get_ratio reports them (decimator / explicit FIR:
+ * interpolation 1); table_length as rfa_ddc_get_mixer / rfa_ddc_mix_info report
+ * it (0 for RFA_IN_F32_INTERLEAVED; a bank plans with its longest table).
+ * plan receives RFA_DDC_PLAN_FIELDS values, indexed by rfa_ddc_plan_field.
+ * RFA_ERR_INVALID for a count below 1 (table_length below 0) or a null plan;
+ * RFA_ERR_UNSUPPORTED for a table rfa_ddc_set_frequencies would reject. */
+enum rfa_ddc_plan_field {
+    RFA_DDC_PLAN_OUTPUTS = 0,     /* P: decimated outputs per workgroup */
+    RFA_DDC_PLAN_THREADS = 1,     /* workgroup size: P rounded up to a multiple of 64 */
+    RFA_DDC_PLAN_CHUNK_TAPS = 2,  /* KC: taps per LDS pass (== taps_per_output when one pass does) */
+    RFA_DDC_PLAN_CHUNKS = 3,      /* passes: ceil(taps_per_output / KC) */
+    RFA_DDC_PLAN_PAD = 4,         /* 1: rows of RFA_DDC_PLAN_ROW samples at an odd pitch; 0: linear */
+    RFA_DDC_PLAN_ROW = 5,         /* LDS row length in samples: max(1, decimation / interpolation) */
+    RFA_DDC_PLAN_LDS_BYTES = 6,   /* dynamic LDS of one workgroup */
+    RFA_DDC_PLAN_FIELDS = 7
+};
+RFA_API int rfa_ddc_tile_plan(int32_t taps_per_output, int32_t interpolation, int32_t decimation,
+                              int32_t table_length, int32_t *plan);
 
 /* ------------------------------------------------------------------------
  * Demodulator: quadrature-rate IQ (what rfa_ddc_process writes, planar float

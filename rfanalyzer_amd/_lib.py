@@ -197,6 +197,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_ddc_bank_synchronize": (ctypes.c_int, [_h]),
         "rfa_ddc_mix_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_ddc_tile_plan": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32)]),
         # demodulator (rfanalyzer_amd/demod.py Demodulator, Receiver)
         "rfa_demod_mode_info": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_int32)] * 4),
         "rfa_bandpass_taps": (ctypes.c_int, [ctypes.c_float] * 6 + [_fp, _fp, ctypes.c_size_t,

@@ -1007,6 +1007,27 @@ int rfa_ddc_mix_info(int input_format, int32_t sample_rate, int64_t frequency, i
     return RFA_OK;
 }
 
+int rfa_ddc_tile_plan(int32_t taps_per_output, int32_t interpolation, int32_t decimation, int32_t table_length,
+                      int32_t *plan) {
+    if (!plan || taps_per_output < 1 || interpolation < 1 || decimation < 1 || table_length < 0)
+        return RFA_ERR_INVALID;
+    if ((size_t)table_length * 8 > (size_t)kDynLds / 2) return RFA_ERR_UNSUPPORTED;   // as rfa_ddc_set_frequencies
+    DdcLaunch a{};
+    a.T = taps_per_output;
+    a.I = interpolation;
+    a.Dd = decimation;
+    a.L = table_length;
+    plan_tiles(a);
+    plan[RFA_DDC_PLAN_OUTPUTS] = a.P;
+    plan[RFA_DDC_PLAN_THREADS] = a.threads;
+    plan[RFA_DDC_PLAN_CHUNK_TAPS] = a.KC;
+    plan[RFA_DDC_PLAN_CHUNKS] = (a.T + a.KC - 1) / a.KC;
+    plan[RFA_DDC_PLAN_PAD] = a.pad;
+    plan[RFA_DDC_PLAN_ROW] = a.D;
+    plan[RFA_DDC_PLAN_LDS_BYTES] = a.lds_bytes;
+    return RFA_OK;
+}
+
 int rfa_ddc_bank_create(int device, int input_format, int32_t sample_rate, int32_t output_sample_rate, int resampler,
                         int32_t n_channels, rfa_ddc_bank **out) {
     if (!out) return RFA_ERR_INVALID;

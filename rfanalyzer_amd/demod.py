@@ -251,6 +251,21 @@ def mix_info(input_format: str, sample_rate: int, frequency: int, channel_freque
     return mf.value, n.value
 
 
+TILE_PLAN_FIELDS = ("P", "threads", "KC", "chunks", "pad", "row", "lds_bytes")   # rfa_ddc_plan_field order
+
+
+def tile_plan(taps_per_output: int, interpolation: int, decimation: int, table_length: int) -> dict:
+    """The workgroup tile plan of a front-end filter (``rfa_ddc_tile_plan``): outputs per
+    workgroup ``P``, ``threads``, taps per LDS pass ``KC`` and the number of passes ``chunks``,
+    ``pad`` (1: rows of ``row`` samples at an odd pitch, 0: linear), ``row`` and ``lds_bytes``.
+    Arguments as ``FrontEnd.ratio()`` and the mixer table length give them (0 for "f32"; a bank
+    plans with its longest table).  Host-only."""
+    out = (ctypes.c_int32 * len(TILE_PLAN_FIELDS))()
+    _lib.check(_lib.lib().rfa_ddc_tile_plan(taps_per_output, interpolation, decimation, table_length, out),
+               "rfa_ddc_tile_plan")
+    return dict(zip(TILE_PLAN_FIELDS, (int(v) for v in out)))
+
+
 class FrontEndBank:
     """``n_channels`` channels out of one raw IQ stream per call (``rfa_ddc_bank_*``): the slots
     share format, rates and filter, each has its own mixer and delay line, and slot k gives
