@@ -31,6 +31,7 @@
  *     analyzer/Resampler.kt:102-110, dsp/RationalResampler.kt:27-127
  *   the two above for K channels of one raw packet         rfa_ddc_bank_*() (channel bank, below)
  *   K Demodulators with their AudioSinks, one set of launches rfa_demod_bank_*() (demodulator bank, below)
+ *   (extension) every channel of a uniform raster per call rfa_pfb_*() (polyphase channelizer, below)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -581,6 +582,81 @@ enum rfa_ddc_plan_field {
 };
 RFA_API int rfa_ddc_tile_plan(int32_t taps_per_output, int32_t interpolation, int32_t decimation,
                               int32_t table_length, int32_t *plan);
+
+/* ------------------------------------------------------------------------
+ * Polyphase channelizer: all n_channels = M channels of the
+ * uniform raster k * Fs / M out of one raw IQ stream per call, for a cost that
+ * does not grow with the channel count.  For channels on a raster it replaces
+ * the front-end channel bank above; arbitrary frequencies stay with the bank.
+ * With x[j] the converted input (s8: b/128, u8: (b-127.4f)/128, s16: s/32768,
+ * float I,Q as it is; j counts samples since creation or reset, x[j] = 0 for
+ * j < 0), real prototype taps h[0..T-1] and integer decimation D, output n is
+ * due once sample i_n = n * D + D - 1 has been consumed (FirFilter's counter)
+ * and channel k is
+ *   y_k[n] = sum_t h[t] * x[i_n - t] * exp(-j 2 pi k (i_n - t) / M)
+ * -- an NCO at k * Fs / M with absolute phase, the FIR, decimation by D.  A
+ * tone at +k * Fs / M lands in channel k with gain sum(h); channels k >= M/2
+ * are the negative offsets (k - M) * Fs / M.  It is computed as a fold
+ *   u_n[r] = sum of h[t] * x[i_n - t] over the t with (i_n - t) mod M == r
+ * (t ascending from 0, product and sum rounded separately) and one forward
+ * M-point DFT over r.  An output's bits do not depend on how the stream is cut
+ * into calls, on the channel selection or on the raw pointer's offset.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_pfb rfa_pfb;
+
+#define RFA_PFB_MIN_CHANNELS 8
+#define RFA_PFB_MAX_CHANNELS 4096
+#define RFA_PFB_MAX_PHASES   16            /* num_taps <= 16 * n_channels */
+
+/* Host only, no device needed: 1 where n_channels = 2^a 3^b 5^c within
+ * RFA_PFB_MIN_CHANNELS .. RFA_PFB_MAX_CHANNELS, else 0. */
+RFA_API int rfa_pfb_supported(int32_t n_channels);
+/* input_format RFA_IN_S8 / _U8 / _S16LE / _F32_INTERLEAVED; 1 <= decimation <=
+ * n_channels; 1 <= num_taps <= RFA_PFB_MAX_PHASES * n_channels (any length, not
+ * only multiples of n_channels).  Arguments are checked before the device is
+ * looked for: RFA_ERR_INVALID first, then RFA_ERR_UNSUPPORTED for an n_channels
+ * rfa_pfb_supported rejects, and RFA_ERR_NODEVICE only for a valid request;
+ * *out is NULL on every failure.  All channels are selected at creation. */
+RFA_API int rfa_pfb_create(int device, int input_format, int32_t n_channels, int32_t decimation, const float *taps,
+                           int32_t num_taps, rfa_pfb **out);
+RFA_API int rfa_pfb_destroy(rfa_pfb *p);
+RFA_API const char *rfa_pfb_last_error(const rfa_pfb *p);
+/* The DFT's radices in stage order (each 2, 3, 4 or 5; their product is
+ * n_channels): *count of them, copied where radices is given (RFA_ERR_SIZE when
+ * cap is smaller).  Any output pointer may be NULL. */
+RFA_API int rfa_pfb_get_plan(const rfa_pfb *p, int32_t *n_channels, int32_t *decimation, int32_t *num_taps,
+                             int32_t *radices, int32_t cap, int32_t *count);
+RFA_API int rfa_pfb_get_taps(const rfa_pfb *p, float *taps, size_t capacity, int32_t *num_taps);
+/* Output slot j is channel channels[j]: entries in 0 .. n_channels - 1 in any
+ * order, repeats allowed, 1 <= count <= n_channels; count 0 or a NULL list
+ * selects all channels in natural order.  Uploaded between calls (drains the
+ * stream).  An invalid list is RFA_ERR_INVALID and leaves the selection as it
+ * was.  The selection changes which rows are written, never their values. */
+RFA_API int rfa_pfb_set_channels(rfa_pfb *p, const int32_t *channels, int32_t count);
+RFA_API int rfa_pfb_get_channels(const rfa_pfb *p, int32_t *channels, size_t capacity, int32_t *count);
+/* The exact output count per channel of the next call of n_samples:
+ * floor((c + n_samples) / D) - floor(c / D) with c samples consumed so far. */
+RFA_API int rfa_pfb_max_outputs(const rfa_pfb *p, size_t n_samples, size_t *n);
+/* out_re / out_im are [selected][channel_stride] device floats, slot j's outputs
+ * at j * channel_stride, time contiguous: the layout rfa_demod_bank_process
+ * reads.  Only the selected rows' first *n_out floats are written.
+ * RFA_ERR_SIZE when channel_stride is smaller than the count (nothing is
+ * enqueued or consumed then).  A call too short for an output still advances
+ * the history and the sample count; n_samples 0 is a no-op.  in may sit at any
+ * sample boundary.  Asynchronous on the handle's stream: two kernel launches
+ * (fold + DFT, history) whatever the channel count; no copy, allocation or
+ * synchronisation. */
+RFA_API int rfa_pfb_process(rfa_pfb *p, const void *in, size_t n_samples, float *out_re, float *out_im,
+                            size_t channel_stride, size_t *n_out);
+/* Same with host buffers; copies and synchronises. */
+RFA_API int rfa_pfb_process_host(rfa_pfb *p, const void *in, size_t n_samples, float *out_re, float *out_im,
+                                 size_t channel_stride, size_t *n_out);
+/* History zeroed, sample count 0: the next call starts a new stream. */
+RFA_API int rfa_pfb_reset(rfa_pfb *p);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_pfb_set_stream(rfa_pfb *p, void *stream);
+RFA_API int rfa_pfb_get_stream(const rfa_pfb *p, void **stream);
+RFA_API int rfa_pfb_synchronize(rfa_pfb *p);
 
 /* ------------------------------------------------------------------------
  * Demodulator: quadrature-rate IQ (what rfa_ddc_process writes, planar float

@@ -198,6 +198,27 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_ddc_mix_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
         "rfa_ddc_tile_plan": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32)]),
+        # polyphase channelizer (rfanalyzer_amd/demod.py Channelizer, RasterReceiverBank)
+        "rfa_pfb_supported": (ctypes.c_int, [ctypes.c_int32]),
+        "rfa_pfb_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, _fp,
+                                          ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_pfb_destroy": (ctypes.c_int, [_h]),
+        "rfa_pfb_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_pfb_get_plan": (ctypes.c_int, [_h] + [ctypes.POINTER(ctypes.c_int32)] * 4
+                             + [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_pfb_get_taps": (ctypes.c_int, [_h, _fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_pfb_set_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+        "rfa_pfb_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.c_size_t,
+                                                ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_pfb_max_outputs": (ctypes.c_int, [_h, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_pfb_process": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t,
+                                           ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_pfb_process_host": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t,
+                                                ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_pfb_reset": (ctypes.c_int, [_h]),
+        "rfa_pfb_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_pfb_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_pfb_synchronize": (ctypes.c_int, [_h]),
         # demodulator (rfanalyzer_amd/demod.py Demodulator, Receiver)
         "rfa_demod_mode_info": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_int32)] * 4),
         "rfa_bandpass_taps": (ctypes.c_int, [ctypes.c_float] * 6 + [_fp, _fp, ctypes.c_size_t,

@@ -1,0 +1,645 @@
+// channelizer.hip -- polyphase channelizer on gfx950 (rfa_pfb_*): all M raster
+// channels k * Fs / M of one raw IQ stream per call, for about the cost of two
+// or three slots of the front-end channel bank (ddc.hip) whatever M is.
+//
+// Channel k of output n (newest input i_n = n * D + D - 1) is
+//   y_k[n] = sum_t h[t] * x[i_n - t] * exp(-j 2 pi k (i_n - t) / M)
+// computed as a fold and one forward DFT:
+//   u_n[r] = sum of h[t] * x[i_n - t] over the t with (i_n - t) mod M == r
+//   y_k[n] = sum_r u_n[r] * exp(-j 2 pi k r / M)
+// The phase is absolute in the sample count, so it never drifts and no rotation
+// follows the DFT.
+//
+// Two launches per call.  pfb_kernel: a workgroup owns NT consecutive output
+// times.  Where the (NT-1) * D + T converted samples they depend on and the taps
+// fit kPfbStageBytes of LDS they are staged there once (every load in flight at
+// the same time, one conversion per sample); else item (time, r) folds its
+// P = ceil(T / M) taps straight from the history or the raw buffer (the raw
+// stream is 2-8 B per sample and is re-read from L2; consecutive r read
+// consecutive samples).  The NT folded rows go through an in-LDS Stockham DFT
+// of radices {4, 2, 3, 5}, and the selected channels are written with time
+// along the lanes: NT = 16 floats, 64 B, per row and burst.
+// pfb_hist_kernel keeps the newest T - 1 converted samples for the next call in
+// the other of two history buffers, so no workgroup reads what another writes.
+//
+// An output's arithmetic is a function of its own window only: every (time, r)
+// item runs the same statements on the same values wherever the tile or call
+// boundary falls (history entries are the stored results of the same
+// conversion), taps are summed t ascending from 0 with product and sum rounded
+// separately (no FMA contraction), and the DFT of one output never mixes with
+// another's.  That makes split, selection, format and pointer offset bit-exact.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/rfa.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kPfbThreads = 256;
+constexpr int kPfbMaxStages = 12;
+constexpr int kPfbTilePoints = 4096;     // NT * M at most: two LDS row sets of 8 B points, 64 KiB + padding
+constexpr int kPfbMaxTimes = 16;         // NT at most: 64 B per row and store burst
+constexpr int kPfbStageBytes = 64 * 1024;  // staged samples + taps at most; above it the fold reads global memory
+
+struct PfbLaunch {
+    const void *raw;
+    long long S;                   // input samples this call
+    const float *hist;             // [re T-1 | im T-1], oldest first, precedes raw[0]
+    float *new_hist;
+    const float *taps;
+    int T, M, Mp, D;               // Mp: LDS row pitch in points, odd
+    int NT;                        // output times per workgroup, a power of two
+    int stage;                     // points of LDS in front of the DFT rows: staged run + taps, 0 = fold from global
+    int run;                       // (NT-1) * D + T: samples a full workgroup depends on
+    long long n0, in0, n_out;      // index of this call's first output / first input since reset
+    const float2 *tw;              // stage s: tw[tw_off[s] + k * (R - 1) + (r - 1)] = exp(-j 2 pi k r / (p R))
+    int nstages;
+    int radix[kPfbMaxStages];
+    int tw_off[kPfbMaxStages];
+    const int *chan;               // slot -> channel
+    int K;
+    long long stride;              // floats between two slots' rows
+    float *out_re, *out_im;
+};
+
+// One complex input sample, converted as the front end converts it before mixing
+// (mix_raw in ddc.hip); g is call-relative, negative values index the history.
+template <int FMT>
+__device__ __forceinline__ float2 pfb_sample(const PfbLaunch &a, long long g) {
+    if (g < 0) return float2{a.hist[a.T - 1 + g], a.hist[2 * (a.T - 1) + g]};
+    if constexpr (FMT == RFA_IN_F32_INTERLEAVED) {
+        return static_cast<const float2 *>(a.raw)[g];
+    } else if constexpr (FMT == RFA_IN_S16LE) {
+        const unsigned v = static_cast<const unsigned *>(a.raw)[g];
+        return float2{(float)(short)(v & 0xffffu) / 32768.0f, (float)(short)(v >> 16) / 32768.0f};
+    } else if constexpr (FMT == RFA_IN_S8) {
+        const unsigned v = static_cast<const unsigned short *>(a.raw)[g];
+        return float2{(float)(signed char)(v & 0xffu) / 128.0f, (float)(signed char)(v >> 8) / 128.0f};
+    } else {
+        const unsigned v = static_cast<const unsigned short *>(a.raw)[g];
+        return float2{((float)(v & 0xffu) - 127.4f) / 128.0f, ((float)(v >> 8) - 127.4f) / 128.0f};
+    }
+}
+
+// One staged sample as its own ds_read_b64 (see lds_ld in ddc.hip: a volatile LDS
+// access keeps neighbours from being fused into ds_read2_b64).
+__device__ __forceinline__ float2 pfb_lds_ld(const float2 *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const v2f v = *(const volatile __attribute__((address_space(3))) v2f *)(p);
+    return float2{v.x, v.y};
+#else
+    return *p;
+#endif
+}
+
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return float2{a.x + b.x, a.y + b.y}; }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return float2{a.x - b.x, a.y - b.y}; }
+__device__ __forceinline__ float2 cmul(float2 a, float2 w) { return float2{a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x}; }
+__device__ __forceinline__ float2 cscale(float s, float2 a) { return float2{s * a.x, s * a.y}; }
+__device__ __forceinline__ float2 mul_mi(float2 m, float2 n) { return float2{m.x + n.y, m.y - n.x}; }   // m - j n
+__device__ __forceinline__ float2 mul_pi(float2 m, float2 n) { return float2{m.x - n.y, m.y + n.x}; }   // m + j n
+
+// One Stockham butterfly of radix R: inputs Q = M / R apart, twiddled by the
+// stage's table (p: product of the radices already done), outputs p apart.
+template <int R>
+__device__ __forceinline__ void pfb_butterfly(const float2 *src, float2 *dst, const float2 *tw, int i, int p, int Q) {
+    const int k = i % p;
+    const int j = (i - k) * R + k;
+    float2 u[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) u[r] = src[i + r * Q];
+    if (p > 1) {
+#pragma unroll
+        for (int r = 1; r < R; r++) u[r] = cmul(u[r], tw[k * (R - 1) + (r - 1)]);
+    }
+    float2 y[R];
+    if constexpr (R == 2) {
+        y[0] = cadd(u[0], u[1]);
+        y[1] = csub(u[0], u[1]);
+    } else if constexpr (R == 4) {
+        const float2 a = cadd(u[0], u[2]), b = csub(u[0], u[2]), c = cadd(u[1], u[3]), d = csub(u[1], u[3]);
+        y[0] = cadd(a, c);
+        y[1] = mul_mi(b, d);
+        y[2] = csub(a, c);
+        y[3] = mul_pi(b, d);
+    } else if constexpr (R == 3) {
+        const float2 t = cadd(u[1], u[2]);
+        const float2 m = csub(u[0], cscale(0.5f, t));
+        const float2 s = cscale(0.86602540378443864676f, csub(u[1], u[2]));
+        y[0] = cadd(u[0], t);
+        y[1] = mul_mi(m, s);
+        y[2] = mul_pi(m, s);
+    } else {
+        constexpr float c1 = 0.30901699437494742410f, c2 = -0.80901699437494742410f;
+        constexpr float s1 = 0.95105651629515357212f, s2 = 0.58778525229247312917f;
+        const float2 a1 = cadd(u[1], u[4]), a2 = cadd(u[2], u[3]), b1 = csub(u[1], u[4]), b2 = csub(u[2], u[3]);
+        const float2 m1 = cadd(cadd(u[0], cscale(c1, a1)), cscale(c2, a2));
+        const float2 m2 = cadd(cadd(u[0], cscale(c2, a1)), cscale(c1, a2));
+        const float2 n1 = cadd(cscale(s1, b1), cscale(s2, b2));
+        const float2 n2 = csub(cscale(s2, b1), cscale(s1, b2));
+        y[0] = cadd(cadd(u[0], a1), a2);
+        y[1] = mul_mi(m1, n1);
+        y[2] = mul_mi(m2, n2);
+        y[3] = mul_pi(m2, n2);
+        y[4] = mul_pi(m1, n1);
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) dst[j + r * p] = y[r];
+}
+
+template <int R>
+__device__ __forceinline__ void pfb_stage(const PfbLaunch &a, const float2 *src, float2 *dst, const float2 *tw, int p,
+                                          int nloc) {
+    const int Q = a.M / R;
+    for (int item = threadIdx.x; item < nloc * Q; item += kPfbThreads) {
+        const int nl = item / Q, i = item - nl * Q;
+        pfb_butterfly<R>(src + nl * a.Mp, dst + nl * a.Mp, tw, i, p, Q);
+    }
+}
+
+template <int FMT>
+__global__ __launch_bounds__(kPfbThreads) void pfb_kernel(PfbLaunch a) {
+    extern __shared__ __attribute__((aligned(16))) float2 pfb_lds[];
+    // [staged run | taps] (a.stage points, absent where the fold reads global memory) | DFT rows x 2
+    float2 *src = pfb_lds + a.stage, *dst = src + a.NT * a.Mp;
+    const int tid = threadIdx.x;
+    const long long m0 = (long long)blockIdx.x * a.NT;
+    const int nloc = (int)min((long long)a.NT, a.n_out - m0);
+    const float2 *xs = pfb_lds;                                  // xs[i]: sample i_first - (T-1) + i
+    const float *hs = reinterpret_cast<const float *>(pfb_lds + a.run);
+    if (a.stage) {
+        const long long g_lo = (a.n0 + m0) * a.D + (a.D - 1) - (a.T - 1) - a.in0;
+        const int span = (nloc - 1) * a.D + a.T;
+        for (int i = tid; i < span; i += kPfbThreads) pfb_lds[i] = pfb_sample<FMT>(a, g_lo + i);
+        float *hw = reinterpret_cast<float *>(pfb_lds + a.run);
+        for (int i = tid; i < a.T; i += kPfbThreads) hw[i] = a.taps[i];
+        __syncthreads();
+    }
+    // fold: item (nl, r) sums the taps t = t0, t0 + M, ... of output n0 + m0 + nl, t0 = (i_n - r) mod M
+    for (int item = tid; item < nloc * a.M; item += kPfbThreads) {
+        const int nl = item / a.M, r = item - nl * a.M;
+        const long long i_abs = (a.n0 + m0 + nl) * a.D + (a.D - 1);
+        int t0 = (int)(i_abs % a.M) - r;
+        if (t0 < 0) t0 += a.M;
+        long long g = i_abs - t0 - a.in0;
+        float2 acc = {0.0f, 0.0f};
+        if (a.stage) {
+            const float2 *x = xs + nl * a.D + (a.T - 1);
+#pragma unroll 4
+            for (int t = t0; t < a.T; t += a.M) {
+                const float2 v = pfb_lds_ld(x - t);
+                const float h = hs[t];
+                acc.x = acc.x + h * v.x;
+                acc.y = acc.y + h * v.y;
+            }
+        } else {
+#pragma unroll 4
+            for (int t = t0; t < a.T; t += a.M, g -= a.M) {
+                const float2 x = pfb_sample<FMT>(a, g);
+                const float h = a.taps[t];
+                acc.x = acc.x + h * x.x;
+                acc.y = acc.y + h * x.y;
+            }
+        }
+        src[nl * a.Mp + r] = acc;
+    }
+    __syncthreads();
+    int p = 1;
+    for (int s = 0; s < a.nstages; s++) {
+        const int R = a.radix[s];
+        const float2 *tw = a.tw + a.tw_off[s];
+        if (R == 4) pfb_stage<4>(a, src, dst, tw, p, nloc);
+        else if (R == 2) pfb_stage<2>(a, src, dst, tw, p, nloc);
+        else if (R == 3) pfb_stage<3>(a, src, dst, tw, p, nloc);
+        else pfb_stage<5>(a, src, dst, tw, p, nloc);
+        __syncthreads();
+        float2 *sw = src;
+        src = dst;
+        dst = sw;
+        p *= R;
+    }
+    // selected channels, time along the lanes
+    const int sh = 31 - __clz(a.NT);
+    for (int item = tid; item < a.K * a.NT; item += kPfbThreads) {
+        const int slot = item >> sh, nl = item & (a.NT - 1);
+        if (nl < nloc) {
+            const float2 v = src[nl * a.Mp + a.chan[slot]];
+            const long long o = (long long)slot * a.stride + m0 + nl;
+            a.out_re[o] = v.x;
+            a.out_im[o] = v.y;
+        }
+    }
+}
+
+// new_hist[t] = sample S - (T-1) + t of the extended sequence [hist | raw].
+template <int FMT>
+__global__ __launch_bounds__(kPfbThreads) void pfb_hist_kernel(PfbLaunch a) {
+    const int t = blockIdx.x * kPfbThreads + threadIdx.x;
+    if (t >= a.T - 1) return;
+    const float2 x = pfb_sample<FMT>(a, a.S - (a.T - 1) + t);
+    a.new_hist[t] = x.x;
+    a.new_hist[a.T - 1 + t] = x.y;
+}
+
+int pfb_lds_bytes(const PfbLaunch &a) { return (a.stage + 2 * a.NT * a.Mp) * (int)sizeof(float2); }
+
+template <int FMT>
+hipError_t pfb_prepare() {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(pfb_kernel<FMT>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               kPfbStageBytes + 2 * (kPfbTilePoints + kPfbMaxTimes) * (int)sizeof(float2));
+}
+
+template <int FMT>
+hipError_t pfb_launch(const PfbLaunch &a, hipStream_t st) {
+    if (a.n_out > 0) {
+        const long long blocks = (a.n_out + a.NT - 1) / a.NT;
+        hipLaunchKernelGGL(pfb_kernel<FMT>, dim3((unsigned)blocks), dim3(kPfbThreads), pfb_lds_bytes(a), st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (a.T > 1) {
+        hipLaunchKernelGGL(pfb_hist_kernel<FMT>, dim3((a.T - 1 + kPfbThreads - 1) / kPfbThreads), dim3(kPfbThreads), 0,
+                           st, a);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------- host plan
+
+// Radices of an M = 2^a 3^b 5^c point DFT: 4s, one 2 for an odd a, 3s, 5s; empty for any other M.
+std::vector<int> pfb_radices(int32_t M) {
+    std::vector<int> r;
+    if (M < RFA_PFB_MIN_CHANNELS || M > RFA_PFB_MAX_CHANNELS) return r;
+    int a = 0, b = 0, c = 0;
+    while (M % 2 == 0) M /= 2, a++;
+    while (M % 3 == 0) M /= 3, b++;
+    while (M % 5 == 0) M /= 5, c++;
+    if (M != 1) return r;
+    r.insert(r.end(), a / 2, 4);
+    r.insert(r.end(), a % 2, 2);
+    r.insert(r.end(), b, 3);
+    r.insert(r.end(), c, 5);
+    return r;
+}
+
+// Stage tables in double, rounded once to float.
+void pfb_twiddles(const std::vector<int> &radix, std::vector<float2> &tw, std::vector<int> &off) {
+    tw.clear();
+    off.clear();
+    long long p = 1;
+    for (int R : radix) {
+        off.push_back((int)tw.size());
+        const long long n = p * R;
+        for (long long k = 0; k < p; k++)
+            for (int r = 1; r < R; r++) {
+                const double ang = -2.0 * M_PI * (double)((k * r) % n) / (double)n;
+                tw.push_back(float2{(float)std::cos(ang), (float)std::sin(ang)});
+            }
+        p = n;
+    }
+}
+
+int pfb_times_per_tile(int M) {
+    int nt = kPfbMaxTimes;
+    while (nt > 1 && nt * M > kPfbTilePoints) nt >>= 1;
+    return nt;
+}
+
+// The tile plan of a handle: NT, and whether the run and the taps are staged in LDS.
+void pfb_plan_tile(PfbLaunch &a) {
+    a.Mp = a.M | 1;
+    a.NT = pfb_times_per_tile(a.M);
+    a.run = (a.NT - 1) * a.D + a.T;
+    const int points = a.run + (a.T + 1) / 2;                    // taps: two floats per point
+    a.stage = points * (int)sizeof(float2) <= kPfbStageBytes ? points : 0;
+}
+
+size_t pfb_sample_bytes(int fmt) {
+    switch (fmt) {
+    case RFA_IN_S8:
+    case RFA_IN_U8: return 2;
+    case RFA_IN_S16LE: return 4;
+    case RFA_IN_F32_INTERLEAVED: return 8;
+    default: return 0;
+    }
+}
+
+}  // namespace
+
+struct rfa_pfb {
+    int device = 0;
+    int fmt = 0;
+    int M = 0, D = 0, T = 0;
+    std::vector<float> taps;
+    std::vector<int> radix, tw_off;
+    std::vector<int32_t> channels;      // slot -> channel
+    hipStream_t stream = nullptr;       // where work is enqueued (own_stream or the caller's)
+    hipStream_t own_stream = nullptr;   // created by the handle; set once rfa_pfb_set_stream is used
+    std::string err;
+    long long in_done = 0;              // samples consumed since creation or reset
+    float *d_taps = nullptr;
+    float2 *d_tw = nullptr;
+    int *d_chan = nullptr;              // M entries
+    float *d_hist[2] = {nullptr, nullptr};
+    int cur = 0;
+    // staging for the _host entry point
+    void *d_in = nullptr;
+    size_t d_in_cap = 0;
+    float *d_out = nullptr;
+    size_t d_out_cap = 0;
+};
+
+namespace {
+
+int pfail(rfa_pfb *p, int code, const std::string &msg) {
+    if (p) p->err = msg;
+    return code;
+}
+
+#define PHIP(p, expr)                                                                  \
+    do {                                                                               \
+        hipError_t _e = (expr);                                                        \
+        if (_e != hipSuccess) return pfail((p), RFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+long long pfb_outputs(const rfa_pfb *p, long long S) { return (p->in_done + S) / p->D - p->in_done / p->D; }
+
+int pfb_upload(rfa_pfb *p) {
+    std::vector<float2> tw;
+    pfb_twiddles(p->radix, tw, p->tw_off);
+    const size_t H = (size_t)std::max(1, p->T - 1);
+    if (hipMalloc(&p->d_taps, p->taps.size() * sizeof(float)) != hipSuccess ||
+        hipMalloc(&p->d_tw, std::max<size_t>(1, tw.size()) * sizeof(float2)) != hipSuccess ||
+        hipMalloc(&p->d_chan, (size_t)p->M * sizeof(int)) != hipSuccess ||
+        hipMalloc(&p->d_hist[0], 2 * H * sizeof(float)) != hipSuccess ||
+        hipMalloc(&p->d_hist[1], 2 * H * sizeof(float)) != hipSuccess)
+        return pfail(p, RFA_ERR_NOMEM, "hipMalloc channelizer tables");
+    PHIP(p, hipMemcpyAsync(p->d_taps, p->taps.data(), p->taps.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    if (!tw.empty())
+        PHIP(p, hipMemcpyAsync(p->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, p->stream));
+    PHIP(p, hipMemcpyAsync(p->d_chan, p->channels.data(), p->channels.size() * sizeof(int), hipMemcpyHostToDevice,
+                           p->stream));
+    PHIP(p, hipMemsetAsync(p->d_hist[0], 0, 2 * H * sizeof(float), p->stream));
+    PHIP(p, hipMemsetAsync(p->d_hist[1], 0, 2 * H * sizeof(float), p->stream));
+    PHIP(p, hipStreamSynchronize(p->stream));
+    PHIP(p, pfb_prepare<RFA_IN_S8>());
+    PHIP(p, pfb_prepare<RFA_IN_U8>());
+    PHIP(p, pfb_prepare<RFA_IN_S16LE>());
+    PHIP(p, pfb_prepare<RFA_IN_F32_INTERLEAVED>());
+    return RFA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rfa_pfb_supported(int32_t n_channels) { return pfb_radices(n_channels).empty() ? 0 : 1; }
+
+int rfa_pfb_create(int device, int input_format, int32_t n_channels, int32_t decimation, const float *taps,
+                   int32_t num_taps, rfa_pfb **out) {
+    if (!out) return RFA_ERR_INVALID;
+    *out = nullptr;
+    if (pfb_sample_bytes(input_format) == 0 || n_channels < 1 || decimation < 1 || !taps || num_taps < 1)
+        return RFA_ERR_INVALID;
+    if (decimation > n_channels || (long long)num_taps > (long long)RFA_PFB_MAX_PHASES * n_channels)
+        return RFA_ERR_INVALID;
+    if (!rfa_pfb_supported(n_channels)) return RFA_ERR_UNSUPPORTED;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
+    if (device < 0 || device >= count) return RFA_ERR_INVALID;
+    rfa_pfb *p = new (std::nothrow) rfa_pfb();
+    if (!p) return RFA_ERR_NOMEM;
+    p->device = device;
+    p->fmt = input_format;
+    p->M = n_channels;
+    p->D = decimation;
+    p->T = num_taps;
+    p->taps.assign(taps, taps + num_taps);
+    p->radix = pfb_radices(n_channels);
+    p->channels.resize(n_channels);
+    for (int k = 0; k < n_channels; k++) p->channels[k] = k;
+    int rc = RFA_OK;
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess)
+        rc = RFA_ERR_HIP;
+    else
+        rc = pfb_upload(p);
+    if (rc != RFA_OK) {
+        rfa_pfb_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return RFA_OK;
+}
+
+int rfa_pfb_destroy(rfa_pfb *p) {
+    if (!p) return RFA_ERR_INVALID;
+    hipSetDevice(p->device);
+    if (p->stream) hipStreamSynchronize(p->stream);
+    for (void *q : {(void *)p->d_taps, (void *)p->d_tw, (void *)p->d_chan, (void *)p->d_hist[0], (void *)p->d_hist[1],
+                    p->d_in, (void *)p->d_out})
+        if (q) hipFree(q);
+    hipStream_t own = p->own_stream ? p->own_stream : p->stream;
+    if (own) hipStreamDestroy(own);
+    delete p;
+    return RFA_OK;
+}
+
+const char *rfa_pfb_last_error(const rfa_pfb *p) { return p ? p->err.c_str() : "null handle"; }
+
+int rfa_pfb_get_plan(const rfa_pfb *p, int32_t *n_channels, int32_t *decimation, int32_t *num_taps, int32_t *radices,
+                     int32_t cap, int32_t *count) {
+    if (!p) return RFA_ERR_INVALID;
+    if (n_channels) *n_channels = p->M;
+    if (decimation) *decimation = p->D;
+    if (num_taps) *num_taps = p->T;
+    if (count) *count = (int32_t)p->radix.size();
+    if (radices) {
+        if (cap < (int32_t)p->radix.size()) return RFA_ERR_SIZE;
+        for (size_t s = 0; s < p->radix.size(); s++) radices[s] = p->radix[s];
+    }
+    return RFA_OK;
+}
+
+int rfa_pfb_get_taps(const rfa_pfb *p, float *taps, size_t capacity, int32_t *num_taps) {
+    if (!p) return RFA_ERR_INVALID;
+    if (num_taps) *num_taps = p->T;
+    if (taps) {
+        if (capacity < p->taps.size()) return RFA_ERR_SIZE;
+        std::memcpy(taps, p->taps.data(), p->taps.size() * sizeof(float));
+    }
+    return RFA_OK;
+}
+
+int rfa_pfb_set_channels(rfa_pfb *p, const int32_t *channels, int32_t count) {
+    if (!p) return RFA_ERR_INVALID;
+    if (count < 0 || count > p->M) return pfail(p, RFA_ERR_INVALID, "channel count outside 0 .. n_channels");
+    std::vector<int32_t> ch;
+    if (!channels || count == 0) {
+        ch.resize(p->M);
+        for (int k = 0; k < p->M; k++) ch[k] = k;
+    } else {
+        ch.assign(channels, channels + count);
+        for (int32_t c : ch)
+            if (c < 0 || c >= p->M) return pfail(p, RFA_ERR_INVALID, "channel outside 0 .. n_channels - 1");
+    }
+    PHIP(p, hipSetDevice(p->device));
+    PHIP(p, hipStreamSynchronize(p->stream));     // an enqueued call still reads the old list
+    PHIP(p, hipMemcpyAsync(p->d_chan, ch.data(), ch.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    PHIP(p, hipStreamSynchronize(p->stream));
+    p->channels = std::move(ch);
+    return RFA_OK;
+}
+
+int rfa_pfb_get_channels(const rfa_pfb *p, int32_t *channels, size_t capacity, int32_t *count) {
+    if (!p) return RFA_ERR_INVALID;
+    if (count) *count = (int32_t)p->channels.size();
+    if (channels) {
+        if (capacity < p->channels.size()) return RFA_ERR_SIZE;
+        std::memcpy(channels, p->channels.data(), p->channels.size() * sizeof(int32_t));
+    }
+    return RFA_OK;
+}
+
+int rfa_pfb_max_outputs(const rfa_pfb *p, size_t n_samples, size_t *n) {
+    if (!p || !n || n_samples > (size_t)1 << 40) return RFA_ERR_INVALID;
+    *n = (size_t)pfb_outputs(p, (long long)n_samples);
+    return RFA_OK;
+}
+
+int rfa_pfb_process(rfa_pfb *p, const void *in, size_t n_samples, float *out_re, float *out_im, size_t channel_stride,
+                    size_t *n_out) {
+    if (!p || !n_out) return RFA_ERR_INVALID;
+    *n_out = 0;
+    if (n_samples == 0) return RFA_OK;
+    const size_t sb = pfb_sample_bytes(p->fmt);
+    if (!in || (uintptr_t)in % sb != 0) return pfail(p, RFA_ERR_INVALID, "input pointer null or misaligned");
+    if (n_samples > (size_t)1 << 40) return pfail(p, RFA_ERR_INVALID, "n_samples too large");
+    const long long S = (long long)n_samples;
+    const long long n = pfb_outputs(p, S);
+    if ((size_t)n > channel_stride) return pfail(p, RFA_ERR_SIZE, "channel_stride smaller than the output count");
+    if (n > 0 && (!out_re || !out_im)) return RFA_ERR_INVALID;
+    PfbLaunch a{};
+    a.raw = in;
+    a.S = S;
+    a.hist = p->d_hist[p->cur];
+    a.new_hist = p->d_hist[p->cur ^ 1];
+    a.taps = p->d_taps;
+    a.T = p->T;
+    a.M = p->M;
+    a.D = p->D;
+    pfb_plan_tile(a);
+    a.n0 = p->in_done / p->D;
+    a.in0 = p->in_done;
+    a.n_out = n;
+    a.tw = p->d_tw;
+    a.nstages = (int)p->radix.size();
+    for (int s = 0; s < a.nstages; s++) a.radix[s] = p->radix[s], a.tw_off[s] = p->tw_off[s];
+    a.chan = p->d_chan;
+    a.K = (int)p->channels.size();
+    a.stride = (long long)channel_stride;
+    a.out_re = out_re;
+    a.out_im = out_im;
+    if ((n + a.NT - 1) / a.NT > (long long)INT32_MAX) return pfail(p, RFA_ERR_INVALID, "call too large for one grid");
+    PHIP(p, hipSetDevice(p->device));
+    hipError_t e = hipSuccess;
+    switch (p->fmt) {
+    case RFA_IN_S8: e = pfb_launch<RFA_IN_S8>(a, p->stream); break;
+    case RFA_IN_U8: e = pfb_launch<RFA_IN_U8>(a, p->stream); break;
+    case RFA_IN_S16LE: e = pfb_launch<RFA_IN_S16LE>(a, p->stream); break;
+    default: e = pfb_launch<RFA_IN_F32_INTERLEAVED>(a, p->stream); break;
+    }
+    if (e != hipSuccess) return pfail(p, RFA_ERR_HIP, std::string("channelizer launch: ") + hipGetErrorString(e));
+    if (a.T > 1) p->cur ^= 1;
+    p->in_done += S;
+    *n_out = (size_t)n;
+    return RFA_OK;
+}
+
+int rfa_pfb_process_host(rfa_pfb *p, const void *in, size_t n_samples, float *out_re, float *out_im,
+                         size_t channel_stride, size_t *n_out) {
+    if (!p || !n_out || (n_samples && !in)) return RFA_ERR_INVALID;
+    *n_out = 0;
+    if (n_samples == 0) return RFA_OK;
+    if (n_samples > (size_t)1 << 40) return pfail(p, RFA_ERR_INVALID, "n_samples too large");
+    const size_t K = p->channels.size();
+    const size_t bytes = n_samples * pfb_sample_bytes(p->fmt);
+    const size_t most = (size_t)pfb_outputs(p, (long long)n_samples);
+    if (most > channel_stride) return pfail(p, RFA_ERR_SIZE, "channel_stride smaller than the output count");
+    if (most > 0 && (!out_re || !out_im)) return RFA_ERR_INVALID;
+    PHIP(p, hipSetDevice(p->device));
+    if (bytes > p->d_in_cap) {
+        if (p->d_in) hipFree(p->d_in);
+        p->d_in = nullptr;
+        p->d_in_cap = 0;
+        if (hipMalloc(&p->d_in, bytes) != hipSuccess) return pfail(p, RFA_ERR_NOMEM, "hipMalloc input staging");
+        p->d_in_cap = bytes;
+    }
+    const size_t pitch = most + 1;
+    if (2 * K * pitch > p->d_out_cap) {
+        if (p->d_out) hipFree(p->d_out);
+        p->d_out = nullptr;
+        p->d_out_cap = 0;
+        if (hipMalloc(&p->d_out, 2 * K * pitch * sizeof(float)) != hipSuccess) return pfail(p, RFA_ERR_NOMEM, "hipMalloc output staging");
+        p->d_out_cap = 2 * K * pitch;
+    }
+    PHIP(p, hipMemcpyAsync(p->d_in, in, bytes, hipMemcpyHostToDevice, p->stream));
+    size_t n = 0;
+    const int rc = rfa_pfb_process(p, p->d_in, n_samples, p->d_out, p->d_out + K * pitch, pitch, &n);
+    if (rc != RFA_OK) return rc;
+    if (n) {
+        PHIP(p, hipMemcpy2DAsync(out_re, channel_stride * sizeof(float), p->d_out, pitch * sizeof(float),
+                                 n * sizeof(float), K, hipMemcpyDeviceToHost, p->stream));
+        PHIP(p, hipMemcpy2DAsync(out_im, channel_stride * sizeof(float), p->d_out + K * pitch, pitch * sizeof(float),
+                                 n * sizeof(float), K, hipMemcpyDeviceToHost, p->stream));
+    }
+    PHIP(p, hipStreamSynchronize(p->stream));
+    *n_out = n;
+    return RFA_OK;
+}
+
+int rfa_pfb_reset(rfa_pfb *p) {
+    if (!p) return RFA_ERR_INVALID;
+    PHIP(p, hipSetDevice(p->device));
+    const size_t H = (size_t)std::max(1, p->T - 1);
+    PHIP(p, hipMemsetAsync(p->d_hist[p->cur], 0, 2 * H * sizeof(float), p->stream));
+    PHIP(p, hipStreamSynchronize(p->stream));
+    p->in_done = 0;
+    return RFA_OK;
+}
+
+int rfa_pfb_set_stream(rfa_pfb *p, void *stream) {
+    if (!p) return RFA_ERR_INVALID;
+    // the history and the channel list are ordered on the handle's stream: drain it first
+    PHIP(p, hipSetDevice(p->device));
+    PHIP(p, hipStreamSynchronize(p->stream));
+    if (p->own_stream == nullptr) p->own_stream = p->stream;
+    p->stream = stream ? (hipStream_t)stream : p->own_stream;
+    return RFA_OK;
+}
+
+int rfa_pfb_get_stream(const rfa_pfb *p, void **stream) {
+    if (!p || !stream) return RFA_ERR_INVALID;
+    *stream = (void *)p->stream;
+    return RFA_OK;
+}
+
+int rfa_pfb_synchronize(rfa_pfb *p) {
+    if (!p) return RFA_ERR_INVALID;
+    PHIP(p, hipSetDevice(p->device));
+    PHIP(p, hipStreamSynchronize(p->stream));
+    return RFA_OK;
+}
+
+}  // extern "C"

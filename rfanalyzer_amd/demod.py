@@ -28,6 +28,11 @@ to 48 kHz audio through ``rfa_demod_*`` (``rfanalyzer_amd/csrc/demod.hip``) -- a
 ``FrontEnd``.  ``DemodulatorBank`` is K demodulators in four launches per call
 (``rfa_demod_bank_*``), each slot bit for bit a ``Demodulator``; ``ReceiverBank`` chains the
 two banks.
+
+``Channelizer`` is the front end for channels on a uniform raster (``rfa_pfb_*``): a polyphase
+filter bank that gives all M channels k * Fs / M of one raw stream in two launches per call,
+for a cost that does not grow with the channel count; ``RasterReceiverBank`` chains it into a
+``DemodulatorBank``.
 """
 from __future__ import annotations
 
@@ -951,6 +956,301 @@ class ReceiverBank:
         if self._cap_for[0] != n:
             self._cap_for = (n, self.front.max_outputs(n))
         cap = self._cap_for[1]
+        if self._re is None or self._re.shape[1] < cap:
+            shape = (self.n_channels, cap)
+            self._re = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+            self._im = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+            self._audio = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+        return self._re.shape[1]
+
+    def process_device(self, raw_ptr: int, n_samples: int) -> list[int]:
+        """Raw samples at a device address -> audio left in the rows of ``self.audio_tensor``;
+        asynchronous on the bank's stream; returns every slot's audio sample count."""
+        cap = self._buffers(0, n_samples)
+        nq = self.front.process_device(raw_ptr, n_samples, self._re.data_ptr(), self._im.data_ptr(), cap)
+        return self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq, self._audio.data_ptr(),
+                                          cap)
+
+    @property
+    def audio_tensor(self):
+        return self._audio
+
+    def process(self, raw_bytes) -> list[np.ndarray]:
+        """One raw input packet (host bytes) -> K float32 audio arrays."""
+        torch = self._torch
+        buf = np.ascontiguousarray(np.frombuffer(raw_bytes, np.uint8)
+                                   if isinstance(raw_bytes, (bytes, bytearray, memoryview))
+                                   else np.asarray(raw_bytes).view(np.uint8).reshape(-1))
+        n = buf.size // BYTES_PER_SAMPLE[self.front.fmt]
+        self._buffers(buf.size, n)
+        self.synchronize()                            # the staging buffer's previous use is over
+        self._raw[:buf.size].copy_(torch.from_numpy(buf.copy()))
+        torch.cuda.synchronize(self._tdev)
+        got = self.process_device(self._raw.data_ptr(), n)
+        self.synchronize()
+        audio = self._audio.cpu().numpy()
+        return [audio[k, :g].copy() for k, g in enumerate(got)]
+
+    def close(self) -> None:
+        if self.front is not None:
+            self.front.close()
+            self.front = None
+        if self.demods is not None:
+            self.demods.close()
+            self.demods = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# ---------------------------------------------------------------- polyphase channelizer
+
+class Channelizer:
+    """All ``n_channels`` = M channels of the uniform raster k * Fs / M out of one raw IQ stream
+    per call (``rfa_pfb_*``, ``rfanalyzer_amd/csrc/channelizer.hip``): the prototype low-pass
+    ``taps`` is folded once per output time and one M-point DFT gives every channel, so a call
+    is two kernel launches and costs about the same whatever the channel count.  M = 2^a 3^b 5^c,
+    8 ... 4096; 1 <= ``decimation`` <= M; up to 16 * M taps.  Channel k is the stream mixed down
+    by k * Fs / M (k >= M/2: the negative offsets), filtered and decimated; ``set_channels``
+    picks which channels are written, slot j being channel ``channels[j]``.  The output rows are
+    what ``DemodulatorBank.process_device`` reads.  Channels that are not on a raster stay with
+    ``FrontEndBank``."""
+
+    def __init__(self, input_format: str, n_channels: int, decimation: int, taps, device: int = 0):
+        if input_format not in FORMATS:
+            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
+        self._h = None
+        self.fmt = FORMATS[input_format]
+        self.n_channels = int(n_channels)
+        self.decimation = int(decimation)
+        self._stream = None
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        h = _lib._h()
+        _lib.check(_lib.lib().rfa_pfb_create(device, self.fmt, self.n_channels, self.decimation,
+                                             taps.ctypes.data_as(_lib._fp), taps.size, ctypes.byref(h)),
+                   "rfa_pfb_create")
+        self._h = h
+        self._n_selected = self.n_channels
+
+    @classmethod
+    def for_raster(cls, input_format: str, sample_rate: int, spacing_hz: int, output_rate: int, device: int = 0):
+        """The channelizer of a raster: ``sample_rate / spacing_hz`` channels, each at ``output_rate``,
+        with the reference's own low-pass design as prototype (``create_low_pass_taps(1, sample_rate,
+        0.375 * spacing, 0.25 * spacing, 60)``, about 10.9 taps per channel).  Both ratios must be
+        whole numbers."""
+        sample_rate, spacing_hz, output_rate = int(sample_rate), int(spacing_hz), int(output_rate)
+        if sample_rate <= 0 or spacing_hz <= 0 or output_rate <= 0:
+            raise ValueError("rates and spacing must be positive")
+        if sample_rate % spacing_hz or sample_rate % output_rate:
+            raise ValueError("sample_rate must be a whole multiple of spacing_hz and of output_rate")
+        taps = create_low_pass_taps(1, sample_rate, 0.375 * spacing_hz, 0.25 * spacing_hz, 60)
+        if taps is None:
+            raise ValueError("the low-pass design rejected the raster")
+        return cls(input_format, sample_rate // spacing_hz, sample_rate // output_rate, taps, device)
+
+    # -- lifetime
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.lib().rfa_pfb_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def _check(self, status: int, where: str) -> None:
+        if status != _lib.RFA_OK:
+            detail = (_lib.lib().rfa_pfb_last_error(self._h) or b"").decode()
+            raise _lib.RfaError(status, where, detail)
+
+    # -- configuration
+    def set_channels(self, channels=None) -> None:
+        """Slot j is channel ``channels[j]`` (any order, repeats allowed); None or empty: all
+        channels in natural order.  An invalid list raises and leaves the selection as it was."""
+        ch = [int(c) for c in channels] if channels is not None else []
+        arr = (ctypes.c_int32 * max(len(ch), 1))(*ch)
+        self._check(_lib.lib().rfa_pfb_set_channels(self._h, arr if ch else None, len(ch)), "rfa_pfb_set_channels")
+        self._n_selected = len(ch) or self.n_channels
+
+    @property
+    def channels(self) -> list[int]:
+        n = ctypes.c_int32(0)
+        out = (ctypes.c_int32 * self.n_channels)()
+        self._check(_lib.lib().rfa_pfb_get_channels(self._h, out, self.n_channels, ctypes.byref(n)),
+                    "rfa_pfb_get_channels")
+        return list(out[:n.value])
+
+    def channel_of(self, frequency: int, channel_frequency: int, sample_rate: int) -> int:
+        """The channel k that holds ``channel_frequency`` when the stream is tuned to ``frequency``;
+        ``ValueError`` where the offset is not on the raster."""
+        num = (int(channel_frequency) - int(frequency)) * self.n_channels
+        if num % int(sample_rate):
+            raise ValueError(f"offset {int(channel_frequency) - int(frequency)} Hz is not on the raster of "
+                             f"{sample_rate}/{self.n_channels} Hz")
+        return (num // int(sample_rate)) % self.n_channels
+
+    def plan(self) -> dict:
+        """{"n_channels", "decimation", "num_taps", "radices"}: the DFT's radices in stage order."""
+        v = [ctypes.c_int32(0) for _ in range(4)]
+        rad = (ctypes.c_int32 * 16)()
+        self._check(_lib.lib().rfa_pfb_get_plan(self._h, ctypes.byref(v[0]), ctypes.byref(v[1]), ctypes.byref(v[2]),
+                                                rad, 16, ctypes.byref(v[3])), "rfa_pfb_get_plan")
+        return {"n_channels": v[0].value, "decimation": v[1].value, "num_taps": v[2].value,
+                "radices": list(rad[:v[3].value])}
+
+    @property
+    def taps(self) -> np.ndarray:
+        n = ctypes.c_int32(0)
+        L = _lib.lib()
+        self._check(L.rfa_pfb_get_taps(self._h, None, 0, ctypes.byref(n)), "rfa_pfb_get_taps")
+        out = np.empty(n.value, np.float32)
+        self._check(L.rfa_pfb_get_taps(self._h, out.ctypes.data_as(_lib._fp), out.size, ctypes.byref(n)),
+                    "rfa_pfb_get_taps")
+        return out
+
+    def max_outputs(self, n_samples: int) -> int:
+        """The exact output count per channel of the next call of ``n_samples``."""
+        n = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_pfb_max_outputs(self._h, n_samples, ctypes.byref(n)), "rfa_pfb_max_outputs")
+        return n.value
+
+    # -- processing
+    def process(self, data) -> list[np.ndarray]:
+        """Host bytes / numpy in -> one complex64 array per selected channel."""
+        buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview))
+                                   else np.asarray(data).view(np.uint8).reshape(-1))
+        n = buf.size // BYTES_PER_SAMPLE[self.fmt]
+        cap = max(self.max_outputs(n), 1)
+        re = np.empty((self._n_selected, cap), np.float32)
+        im = np.empty((self._n_selected, cap), np.float32)
+        got = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_pfb_process_host(self._h, buf.ctypes.data, n, re.ctypes.data, im.ctypes.data, cap,
+                                                    ctypes.byref(got)), "rfa_pfb_process_host")
+        out = np.empty((self._n_selected, got.value), np.complex64)
+        out.real, out.imag = re[:, :got.value], im[:, :got.value]
+        return list(out)
+
+    def process_device(self, in_ptr: int, n_samples: int, re_ptr: int, im_ptr: int, channel_stride: int) -> int:
+        """Device pointers, outputs [selected][channel_stride] floats; asynchronous on the handle's
+        stream; returns the output count per channel."""
+        got = ctypes.c_size_t(0)
+        self._check(_lib.lib().rfa_pfb_process(self._h, in_ptr, n_samples, re_ptr, im_ptr, channel_stride,
+                                               ctypes.byref(got)), "rfa_pfb_process")
+        return got.value
+
+    def process_tensor(self, raw, out_re, out_im) -> int:
+        """torch.cuda tensors: raw bytes (contiguous) -> float32 outputs of shape [selected, stride],
+        on torch's current stream (see ``FrontEnd.process_tensor``)."""
+        import torch
+
+        cur = torch.cuda.current_stream(raw.device).cuda_stream
+        if cur != self._stream:
+            self.set_stream(cur)
+        n = raw.numel() * raw.element_size() // BYTES_PER_SAMPLE[self.fmt]
+        if out_re.shape != out_im.shape or out_re.dim() != 2 or out_re.shape[0] != self._n_selected:
+            raise ValueError(f"out_re and out_im must both have shape [{self._n_selected}, stride]")
+        if not (out_re.is_contiguous() and out_im.is_contiguous()):
+            raise ValueError("out_re and out_im must be contiguous")
+        return self.process_device(raw.data_ptr(), n, out_re.data_ptr(), out_im.data_ptr(), out_re.shape[1])
+
+    def reset(self) -> None:
+        """History zeroed, sample count 0."""
+        self._check(_lib.lib().rfa_pfb_reset(self._h), "rfa_pfb_reset")
+
+    def set_stream(self, stream_ptr: int | None) -> None:
+        """Enqueue on exactly this hipStream_t (None: the handle's own stream)."""
+        self._check(_lib.lib().rfa_pfb_set_stream(self._h, stream_ptr or None), "rfa_pfb_set_stream")
+        self._stream = stream_ptr or None
+
+    def synchronize(self) -> None:
+        self._check(_lib.lib().rfa_pfb_synchronize(self._h), "rfa_pfb_synchronize")
+
+    @property
+    def stream(self) -> int:
+        s = _lib._vp()
+        self._check(_lib.lib().rfa_pfb_get_stream(self._h, ctypes.byref(s)), "rfa_pfb_get_stream")
+        return s.value or 0
+
+
+class RasterReceiverBank:
+    """Raw IQ bytes -> one audio stream per raster channel: a ``Channelizer.for_raster`` at the
+    modes' common quadrature rate feeding a ``DemodulatorBank``, device to device on one stream,
+    2 + 4 launches per packet whatever the channel count.  Slot k demodulates raster channel
+    ``channels[k]`` (default 0, 1, ...) in mode ``modes[k]``; its audio equals, bit for bit, a
+    ``DemodulatorBank`` fed the ``Channelizer``'s own output.  Every mode must have the same
+    quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``)."""
+
+    def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0):
+        import torch
+
+        modes = list(modes)
+        if not modes:
+            raise ValueError("at least one mode")
+        rates = {mode_info(m)[0] for m in modes}
+        if len(rates) != 1:
+            raise ValueError(f"the modes' quadrature rates differ: {sorted(rates)}")
+        channels = list(range(len(modes))) if channels is None else [int(c) for c in channels]
+        if len(channels) != len(modes):
+            raise ValueError(f"{len(modes)} channels expected, got {len(channels)}")
+        self._torch = torch
+        self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
+        self._tdev = torch.device("cuda", device)
+        self.quadrature_rate = rates.pop()
+        self.demods, self.front = None, None
+        self._n_channels = len(modes)
+        self._raw = self._re = self._im = self._audio = None
+        try:
+            self.demods = DemodulatorBank(modes, device)
+            self.front = Channelizer.for_raster(input_format, self.sample_rate, spacing_hz, self.quadrature_rate,
+                                                device)
+            self.front.set_channels(channels)
+            self.set_stream(None)
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def n_channels(self) -> int:
+        return self._n_channels
+
+    @property
+    def channels(self) -> list[int]:
+        return self.front.channels
+
+    def mode(self, k: int) -> int:
+        return self.demods.mode(k)
+
+    def set_mode(self, k: int, mode) -> None:
+        """Slot k's DemodulationMode; only to a mode of the bank's quadrature rate."""
+        if mode_info(mode)[0] != self.quadrature_rate:
+            raise ValueError(f"mode {mode!r} has quadrature rate {mode_info(mode)[0]}, the bank runs at "
+                             f"{self.quadrature_rate}")
+        self.demods.set_mode(k, mode)
+
+    def set_stream(self, stream_ptr: int | None) -> None:
+        """Enqueue every stage on exactly this hipStream_t (None: the demodulator bank's own)."""
+        self.demods.set_stream(stream_ptr)
+        self.front.set_stream(self.demods.stream)
+
+    def synchronize(self) -> None:
+        self.demods.synchronize()
+
+    def _buffers(self, nbytes: int, n: int) -> int:
+        torch = self._torch
+        if self._raw is None or self._raw.numel() < nbytes:
+            self._raw = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self._tdev)
+        cap = n // self.front.decimation + 1          # an upper bound of any call of n samples
         if self._re is None or self._re.shape[1] < cap:
             shape = (self.n_channels, cap)
             self._re = torch.empty(shape, dtype=torch.float32, device=self._tdev)
