@@ -31,7 +31,8 @@
  *     analyzer/Resampler.kt:102-110, dsp/RationalResampler.kt:27-127
  *   the two above for K channels of one raw packet         rfa_ddc_bank_*() (channel bank, below)
  *   K Demodulators with their AudioSinks, one set of launches rfa_demod_bank_*() (demodulator bank, below)
- *   (extension) every channel of a uniform raster per call rfa_pfb_*() (polyphase channelizer, below)
+ *   (extension) every channel of a uniform raster per call rfa_pfb_*() (polyphase channelizer, below;
+ *     rfa_pfb_create_rational: at any source sample rate)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -657,6 +658,53 @@ RFA_API int rfa_pfb_reset(rfa_pfb *p);
 RFA_API int rfa_pfb_set_stream(rfa_pfb *p, void *stream);
 RFA_API int rfa_pfb_get_stream(const rfa_pfb *p, void **stream);
 RFA_API int rfa_pfb_synchronize(rfa_pfb *p);
+
+/* Rational-rate channelizer: the same M raster channels at
+ * L / D times the input rate, 1 <= L <= D <= L * M, gcd(L, D) = 1, so a raster
+ * runs at any source rate (RationalResampler's freedom, dsp/RationalResampler.kt).
+ * x[j] as above; g[0..T-1] are the real prototype taps at rate L * Fs, g[s] = 0
+ * for s >= T, Tp = ceil(T / L) taps per output.  Output n has phase
+ * p_n = (n * D) mod L and newest sample m_n = floor(n * D / L), both from 64-bit
+ * integers, and channel k is
+ *   y_k[n] = sum_{t=0..Tp-1} g[p_n + t * L] * x[m_n - t] * exp(-j 2 pi k (m_n - t) / M)
+ * computed as the fold
+ *   u_n[r] = sum of g[p_n + t * L] * x[m_n - t] over the t with (m_n - t) mod M == r
+ * (t ascending from 0, product and sum rounded separately) and the same forward
+ * M-point DFT over r.  The NCO's phase is the integer input sample index, so
+ * nothing drifts.  Output n is due once sample m_n has been consumed: after c
+ * samples in total ceil(c * L / D) outputs have been produced (0 for c = 0), so
+ * a call that takes the count from c0 to c1 yields ceil(c1 L / D) - ceil(c0 L / D)
+ * per channel -- RationalResampler.resample's counter (ctr starts at 0,
+ * RationalResampler.kt:101-150); channel 0 is that class's output on the unmixed
+ * stream.  The bit-exactness rules of rfa_pfb_process hold unchanged; the window
+ * of an output is always the Tp samples m_n - Tp + 1 .. m_n (a padding tap
+ * multiplies its sample like any other, so a NaN there reaches the output).
+ * L = 1 is allowed and keeps this convention, m_n = n * D: output 0 is due with
+ * the first sample.  That is NOT rfa_pfb_create's i_n = n * D + D - 1; a handle
+ * of rfa_pfb_create(.., D, ..) and one of rfa_pfb_create_rational(.., 1, D, ..)
+ * sample the same filter D - 1 input samples apart. */
+#define RFA_PFB_MAX_INTERPOLATION 64       /* every app rate to 48 / 96 / 384 kHz needs at most 48 / 125 */
+
+/* As rfa_pfb_create with 1 <= interpolation <= RFA_PFB_MAX_INTERPOLATION,
+ * interpolation <= decimation <= interpolation * n_channels, gcd 1, and
+ * 1 <= num_taps <= RFA_PFB_MAX_PHASES * n_channels * interpolation.  Errors in
+ * the same order: RFA_ERR_INVALID (gcd != 1 and interpolation > decimation
+ * included), then RFA_ERR_UNSUPPORTED, then RFA_ERR_NODEVICE; *out is NULL on
+ * every failure.  The handle is an rfa_pfb: every entry above works on it;
+ * rfa_pfb_get_plan reports decimation D and num_taps T (the prototype's length),
+ * rfa_pfb_get_taps the prototype, rfa_pfb_max_outputs / rfa_pfb_process the
+ * count rule above, and the history holds Tp - 1 samples. */
+RFA_API int rfa_pfb_create_rational(int device, int input_format, int32_t n_channels, int32_t interpolation,
+                                    int32_t decimation, const float *taps, int32_t num_taps, rfa_pfb **out);
+/* (L, D, Tp); on a handle of rfa_pfb_create (1, D, T).  Any pointer may be NULL. */
+RFA_API int rfa_pfb_get_ratio(const rfa_pfb *p, int32_t *interpolation, int32_t *decimation,
+                              int32_t *taps_per_output);
+/* Host only, no handle and no device needed: the count rule, *n = ceil((consumed
+ * + n_samples) L / D) - ceil(consumed L / D).  RFA_ERR_INVALID for a ratio
+ * rfa_pfb_create_rational rejects on its own (L < 1, L > RFA_PFB_MAX_INTERPOLATION,
+ * L > D, gcd != 1), a null n, or consumed + n_samples >= 2^53. */
+RFA_API int rfa_pfb_rational_outputs(int32_t interpolation, int32_t decimation, uint64_t consumed, size_t n_samples,
+                                     size_t *n);
 
 /* ------------------------------------------------------------------------
  * Demodulator: quadrature-rate IQ (what rfa_ddc_process writes, planar float

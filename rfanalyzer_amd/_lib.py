@@ -25,6 +25,8 @@ RFA_ERR_NOMEM = -5
 RFA_ERR_HIP = -6
 RFA_ERR_STATE = -7
 
+RFA_PFB_MAX_INTERPOLATION = 64      # include/rfa.h
+
 WINDOWS = {"blackman": 0, "hann": 1, "none": 2}
 FORMATS = {"s8": 0, "u8": 1, "s16": 2, "f32": 3, "f32p": 4}
 BYTES_PER_SAMPLE = {0: 2, 1: 2, 2: 4, 3: 8, 4: 8}
@@ -219,6 +221,11 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_pfb_set_stream": (ctypes.c_int, [_h, _vp]),
         "rfa_pfb_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
         "rfa_pfb_synchronize": (ctypes.c_int, [_h]),
+        "rfa_pfb_create_rational": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_int32, _fp, ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_pfb_get_ratio": (ctypes.c_int, [_h] + [ctypes.POINTER(ctypes.c_int32)] * 3),
+        "rfa_pfb_rational_outputs": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t,
+                                                    ctypes.POINTER(ctypes.c_size_t)]),
         # demodulator (rfanalyzer_amd/demod.py Demodulator, Receiver)
         "rfa_demod_mode_info": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_int32)] * 4),
         "rfa_bandpass_taps": (ctypes.c_int, [ctypes.c_float] * 6 + [_fp, _fp, ctypes.c_size_t,

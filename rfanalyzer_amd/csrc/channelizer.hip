@@ -28,6 +28,10 @@
 // conversion), taps are summed t ascending from 0 with product and sum rounded
 // separately (no FMA contraction), and the DFT of one output never mixes with
 // another's.  That makes split, selection, format and pointer offset bit-exact.
+//
+// rfa_pfb_create_rational runs the same raster at L / D times the input rate:
+// pfb_rational_kernel below folds with one of L sub-filters per output and shares
+// everything else; pfb_kernel is the code the integer entry launches, unchanged.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -251,7 +255,147 @@ __global__ __launch_bounds__(kPfbThreads) void pfb_hist_kernel(PfbLaunch a) {
     a.new_hist[a.T - 1 + t] = x.y;
 }
 
+// ---------------------------------------------------------------- rational rate (rfa_pfb_create_rational)
+//
+// Output n has phase p_n = (n * D) mod L and newest sample m_n = floor(n * D / L):
+//   y_k[n] = sum_{t < Tp} g[p_n + t * L] * x[m_n - t] * exp(-j 2 pi k (m_n - t) / M),  Tp = ceil(T / L)
+// The phase of the NCO is still the integer sample index, so only the fold differs from
+// pfb_kernel: item (time, r) sums gp[p_n][t] * x[m_n - t] over t = t0, t0 + M, ... < Tp with
+// t0 = (m_n - r) mod M.  The taps sit on the device phase-major, gp[p][t] = g[p + t * L], zero
+// padded to Tp per phase, so an item walks one row with stride M and consecutive r read
+// neighbouring taps.  The launch's `a` is a PfbLaunch with T = Tp and taps = gp: pfb_sample,
+// the Stockham stages and pfb_hist_kernel (history of Tp - 1 samples) are the integer path's.
+//
+// A tile of NT times spans at most ceil((NT-1) * D / L) + Tp samples and min(NT, L) different
+// phases (gcd(L, D) = 1).  Three plans, chosen by pfb_plan_rational under the same
+// kPfbStageBytes rule: run and the tile's tap rows staged; run staged, taps from global
+// memory (the table is re-read from L2); run and taps from global memory.
+struct PfbRatLaunch {
+    PfbLaunch a;                   // T: taps per output Tp; taps: gp[L][Tp]; run: ceil((NT-1) D / L) + Tp
+    int L;
+    int stage_x;                   // 1: the run is staged at pfb_lds[0 .. run)
+    int tap_rows;                  // tap rows staged behind the run: L (row = phase) where L <= NT, else NT
+                                   // (row = time); 0: taps are read from global memory
+};
+
+// The stage loop and the store of pfb_kernel, which stays as it is.
+__device__ __forceinline__ void pfb_dft_store(const PfbLaunch &a, float2 *src, float2 *dst, long long m0, int nloc) {
+    const int tid = threadIdx.x;
+    int p = 1;
+    for (int s = 0; s < a.nstages; s++) {
+        const int R = a.radix[s];
+        const float2 *tw = a.tw + a.tw_off[s];
+        if (R == 4) pfb_stage<4>(a, src, dst, tw, p, nloc);
+        else if (R == 2) pfb_stage<2>(a, src, dst, tw, p, nloc);
+        else if (R == 3) pfb_stage<3>(a, src, dst, tw, p, nloc);
+        else pfb_stage<5>(a, src, dst, tw, p, nloc);
+        __syncthreads();
+        float2 *sw = src;
+        src = dst;
+        dst = sw;
+        p *= R;
+    }
+    const int sh = 31 - __clz(a.NT);
+    for (int item = tid; item < a.K * a.NT; item += kPfbThreads) {
+        const int slot = item >> sh, nl = item & (a.NT - 1);
+        if (nl < nloc) {
+            const float2 v = src[nl * a.Mp + a.chan[slot]];
+            const long long o = (long long)slot * a.stride + m0 + nl;
+            a.out_re[o] = v.x;
+            a.out_im[o] = v.y;
+        }
+    }
+}
+
+template <int FMT>
+__global__ __launch_bounds__(kPfbThreads) void pfb_rational_kernel(PfbRatLaunch b) {
+    extern __shared__ __attribute__((aligned(16))) float2 pfb_lds[];
+    __shared__ int t_dm[kPfbMaxTimes], t_ph[kPfbMaxTimes], t_mm[kPfbMaxTimes];   // m_n - m_first, p_n, m_n mod M
+    const PfbLaunch &a = b.a;
+    // [staged run | staged tap rows] (a.stage points) | DFT rows x 2
+    float2 *src = pfb_lds + a.stage, *dst = src + a.NT * a.Mp;
+    const int tid = threadIdx.x;
+    const long long m0 = (long long)blockIdx.x * a.NT;
+    const int nloc = (int)min((long long)a.NT, a.n_out - m0);
+    const long long n_first = a.n0 + m0;
+    const long long m_first = n_first * a.D / b.L;
+    if (tid < nloc) {
+        const long long nd = (n_first + tid) * a.D, m = nd / b.L;
+        t_dm[tid] = (int)(m - m_first);
+        t_ph[tid] = (int)(nd - m * b.L);
+        t_mm[tid] = (int)(m % a.M);
+    }
+    const float2 *xs = pfb_lds;                                  // xs[i]: sample m_first - (Tp-1) + i
+    const float *gs = reinterpret_cast<const float *>(pfb_lds + a.run);
+    const bool by_phase = b.L <= a.NT;
+    if (b.stage_x) {
+        const long long m_last = (n_first + nloc - 1) * a.D / b.L;
+        const long long g_lo = m_first - (a.T - 1) - a.in0;
+        const int span = (int)(m_last - m_first) + a.T;
+        for (int i = tid; i < span; i += kPfbThreads) pfb_lds[i] = pfb_sample<FMT>(a, g_lo + i);
+        float *gw = reinterpret_cast<float *>(pfb_lds + a.run);
+        for (int row = 0; row < b.tap_rows; row++) {
+            const int ph = by_phase ? row : (int)(((n_first + row) * a.D) % b.L);
+            for (int t = tid; t < a.T; t += kPfbThreads) gw[row * a.T + t] = a.taps[(long long)ph * a.T + t];
+        }
+    }
+    __syncthreads();
+    for (int item = tid; item < nloc * a.M; item += kPfbThreads) {
+        const int nl = item / a.M, r = item - nl * a.M;
+        int t0 = t_mm[nl] - r;
+        if (t0 < 0) t0 += a.M;
+        float2 acc = {0.0f, 0.0f};
+        if (b.stage_x) {
+            const float2 *x = xs + t_dm[nl] + (a.T - 1);
+            const float *g = b.tap_rows ? gs + (by_phase ? t_ph[nl] : nl) * a.T : a.taps + (long long)t_ph[nl] * a.T;
+#pragma unroll 4
+            for (int t = t0; t < a.T; t += a.M) {
+                const float2 v = pfb_lds_ld(x - t);
+                const float h = g[t];
+                acc.x = acc.x + h * v.x;
+                acc.y = acc.y + h * v.y;
+            }
+        } else {
+            const float *g = a.taps + (long long)t_ph[nl] * a.T;
+            long long j = m_first + t_dm[nl] - t0 - a.in0;
+#pragma unroll 4
+            for (int t = t0; t < a.T; t += a.M, j -= a.M) {
+                const float2 x = pfb_sample<FMT>(a, j);
+                const float h = g[t];
+                acc.x = acc.x + h * x.x;
+                acc.y = acc.y + h * x.y;
+            }
+        }
+        src[nl * a.Mp + r] = acc;
+    }
+    __syncthreads();
+    pfb_dft_store(a, src, dst, m0, nloc);
+}
+
 int pfb_lds_bytes(const PfbLaunch &a) { return (a.stage + 2 * a.NT * a.Mp) * (int)sizeof(float2); }
+
+template <int FMT>
+hipError_t pfb_rational_prepare() {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(pfb_rational_kernel<FMT>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               kPfbStageBytes + 2 * (kPfbTilePoints + kPfbMaxTimes) * (int)sizeof(float2));
+}
+
+template <int FMT>
+hipError_t pfb_rational_launch(const PfbRatLaunch &b, hipStream_t st) {
+    if (b.a.n_out > 0) {
+        const long long blocks = (b.a.n_out + b.a.NT - 1) / b.a.NT;
+        hipLaunchKernelGGL(pfb_rational_kernel<FMT>, dim3((unsigned)blocks), dim3(kPfbThreads), pfb_lds_bytes(b.a), st, b);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (b.a.T > 1) {
+        hipLaunchKernelGGL(pfb_hist_kernel<FMT>, dim3((b.a.T - 1 + kPfbThreads - 1) / kPfbThreads), dim3(kPfbThreads), 0,
+                           st, b.a);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
 
 template <int FMT>
 hipError_t pfb_prepare() {
@@ -326,6 +470,33 @@ void pfb_plan_tile(PfbLaunch &a) {
     a.stage = points * (int)sizeof(float2) <= kPfbStageBytes ? points : 0;
 }
 
+// The tile plan of a rational handle (b.a.T = Tp, b.a.M, b.a.D and b.L set): NT as above; the run
+// is staged where its 8 B per sample fit kPfbStageBytes, and the tile's min(NT, L) tap rows of
+// Tp floats behind it where both fit.
+void pfb_plan_rational(PfbRatLaunch &b) {
+    PfbLaunch &a = b.a;
+    a.Mp = a.M | 1;
+    a.NT = pfb_times_per_tile(a.M);
+    a.run = (int)(((long long)(a.NT - 1) * a.D + b.L - 1) / b.L) + a.T;
+    const long long rows = std::min(a.NT, b.L);
+    const long long tap_points = (rows * a.T + 1) / 2;
+    b.stage_x = (long long)a.run * (long long)sizeof(float2) <= kPfbStageBytes;
+    b.tap_rows = b.stage_x && (a.run + tap_points) * (long long)sizeof(float2) <= kPfbStageBytes ? (int)rows : 0;
+    a.stage = b.stage_x ? a.run + (b.tap_rows ? (int)tap_points : 0) : 0;
+}
+
+long long pfb_gcd(long long a, long long b) {
+    while (b) {
+        const long long t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+// Outputs due once c samples are consumed: ceil(c * L / D); c < 2^53 and L <= 64 keep the product in range.
+long long pfb_rational_count(long long c, int L, int D) { return (c * L + D - 1) / D; }
+
 size_t pfb_sample_bytes(int fmt) {
     switch (fmt) {
     case RFA_IN_S8:
@@ -342,7 +513,11 @@ struct rfa_pfb {
     int device = 0;
     int fmt = 0;
     int M = 0, D = 0, T = 0;
+    int L = 1;                          // interpolation; above 1 only on a rational handle
+    int Th = 0;                         // taps per output: T, or Tp = ceil(T / L) on a rational handle
+    bool rational = false;              // created by rfa_pfb_create_rational (L = 1 included: m_n = n * D)
     std::vector<float> taps;
+    std::vector<float> gp;              // rational: the device table gp[L][Tp], gp[p][t] = taps[p + t * L]
     std::vector<int> radix, tw_off;
     std::vector<int32_t> channels;      // slot -> channel
     hipStream_t stream = nullptr;       // where work is enqueued (own_stream or the caller's)
@@ -374,19 +549,23 @@ int pfail(rfa_pfb *p, int code, const std::string &msg) {
         if (_e != hipSuccess) return pfail((p), RFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
-long long pfb_outputs(const rfa_pfb *p, long long S) { return (p->in_done + S) / p->D - p->in_done / p->D; }
+long long pfb_outputs(const rfa_pfb *p, long long S) {
+    if (p->rational) return pfb_rational_count(p->in_done + S, p->L, p->D) - pfb_rational_count(p->in_done, p->L, p->D);
+    return (p->in_done + S) / p->D - p->in_done / p->D;
+}
 
 int pfb_upload(rfa_pfb *p) {
     std::vector<float2> tw;
     pfb_twiddles(p->radix, tw, p->tw_off);
-    const size_t H = (size_t)std::max(1, p->T - 1);
-    if (hipMalloc(&p->d_taps, p->taps.size() * sizeof(float)) != hipSuccess ||
+    const size_t H = (size_t)std::max(1, p->Th - 1);
+    const std::vector<float> &dtaps = p->rational ? p->gp : p->taps;
+    if (hipMalloc(&p->d_taps, dtaps.size() * sizeof(float)) != hipSuccess ||
         hipMalloc(&p->d_tw, std::max<size_t>(1, tw.size()) * sizeof(float2)) != hipSuccess ||
         hipMalloc(&p->d_chan, (size_t)p->M * sizeof(int)) != hipSuccess ||
         hipMalloc(&p->d_hist[0], 2 * H * sizeof(float)) != hipSuccess ||
         hipMalloc(&p->d_hist[1], 2 * H * sizeof(float)) != hipSuccess)
         return pfail(p, RFA_ERR_NOMEM, "hipMalloc channelizer tables");
-    PHIP(p, hipMemcpyAsync(p->d_taps, p->taps.data(), p->taps.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
+    PHIP(p, hipMemcpyAsync(p->d_taps, dtaps.data(), dtaps.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
     if (!tw.empty())
         PHIP(p, hipMemcpyAsync(p->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, p->stream));
     PHIP(p, hipMemcpyAsync(p->d_chan, p->channels.data(), p->channels.size() * sizeof(int), hipMemcpyHostToDevice,
@@ -398,6 +577,27 @@ int pfb_upload(rfa_pfb *p) {
     PHIP(p, pfb_prepare<RFA_IN_U8>());
     PHIP(p, pfb_prepare<RFA_IN_S16LE>());
     PHIP(p, pfb_prepare<RFA_IN_F32_INTERLEAVED>());
+    if (p->rational) {
+        PHIP(p, pfb_rational_prepare<RFA_IN_S8>());
+        PHIP(p, pfb_rational_prepare<RFA_IN_U8>());
+        PHIP(p, pfb_rational_prepare<RFA_IN_S16LE>());
+        PHIP(p, pfb_rational_prepare<RFA_IN_F32_INTERLEAVED>());
+    }
+    return RFA_OK;
+}
+
+// The device part of both create entries: stream, tables, history.
+int pfb_finish_create(rfa_pfb *p, rfa_pfb **out) {
+    int rc = RFA_OK;
+    if (hipSetDevice(p->device) != hipSuccess || hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess)
+        rc = RFA_ERR_HIP;
+    else
+        rc = pfb_upload(p);
+    if (rc != RFA_OK) {
+        rfa_pfb_destroy(p);
+        return rc;
+    }
+    *out = p;
     return RFA_OK;
 }
 
@@ -426,20 +626,64 @@ int rfa_pfb_create(int device, int input_format, int32_t n_channels, int32_t dec
     p->M = n_channels;
     p->D = decimation;
     p->T = num_taps;
+    p->Th = num_taps;
     p->taps.assign(taps, taps + num_taps);
     p->radix = pfb_radices(n_channels);
     p->channels.resize(n_channels);
     for (int k = 0; k < n_channels; k++) p->channels[k] = k;
-    int rc = RFA_OK;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess)
-        rc = RFA_ERR_HIP;
-    else
-        rc = pfb_upload(p);
-    if (rc != RFA_OK) {
-        rfa_pfb_destroy(p);
-        return rc;
-    }
-    *out = p;
+    return pfb_finish_create(p, out);
+}
+
+int rfa_pfb_create_rational(int device, int input_format, int32_t n_channels, int32_t interpolation, int32_t decimation,
+                            const float *taps, int32_t num_taps, rfa_pfb **out) {
+    if (!out) return RFA_ERR_INVALID;
+    *out = nullptr;
+    if (pfb_sample_bytes(input_format) == 0 || n_channels < 1 || interpolation < 1 || decimation < 1 || !taps ||
+        num_taps < 1)
+        return RFA_ERR_INVALID;
+    if (interpolation > RFA_PFB_MAX_INTERPOLATION || interpolation > decimation ||
+        (long long)decimation > (long long)interpolation * n_channels || pfb_gcd(interpolation, decimation) != 1 ||
+        (long long)num_taps > (long long)RFA_PFB_MAX_PHASES * n_channels * interpolation)
+        return RFA_ERR_INVALID;
+    if (!rfa_pfb_supported(n_channels)) return RFA_ERR_UNSUPPORTED;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
+    if (device < 0 || device >= count) return RFA_ERR_INVALID;
+    rfa_pfb *p = new (std::nothrow) rfa_pfb();
+    if (!p) return RFA_ERR_NOMEM;
+    p->device = device;
+    p->fmt = input_format;
+    p->M = n_channels;
+    p->L = interpolation;
+    p->D = decimation;
+    p->T = num_taps;
+    p->Th = (num_taps + interpolation - 1) / interpolation;
+    p->rational = true;
+    p->taps.assign(taps, taps + num_taps);
+    p->gp.assign((size_t)p->L * p->Th, 0.0f);
+    for (int s = 0; s < num_taps; s++) p->gp[(size_t)(s % p->L) * p->Th + s / p->L] = taps[s];
+    p->radix = pfb_radices(n_channels);
+    p->channels.resize(n_channels);
+    for (int k = 0; k < n_channels; k++) p->channels[k] = k;
+    return pfb_finish_create(p, out);
+}
+
+int rfa_pfb_get_ratio(const rfa_pfb *p, int32_t *interpolation, int32_t *decimation, int32_t *taps_per_output) {
+    if (!p) return RFA_ERR_INVALID;
+    if (interpolation) *interpolation = p->L;
+    if (decimation) *decimation = p->D;
+    if (taps_per_output) *taps_per_output = p->Th;
+    return RFA_OK;
+}
+
+int rfa_pfb_rational_outputs(int32_t interpolation, int32_t decimation, uint64_t consumed, size_t n_samples, size_t *n) {
+    constexpr uint64_t lim = (uint64_t)1 << 53;
+    if (!n || interpolation < 1 || interpolation > RFA_PFB_MAX_INTERPOLATION || decimation < interpolation ||
+        pfb_gcd(interpolation, decimation) != 1)
+        return RFA_ERR_INVALID;
+    if (consumed >= lim || (uint64_t)n_samples >= lim || consumed + (uint64_t)n_samples >= lim) return RFA_ERR_INVALID;
+    *n = (size_t)(pfb_rational_count((long long)(consumed + n_samples), interpolation, decimation) -
+                  pfb_rational_count((long long)consumed, interpolation, decimation));
     return RFA_OK;
 }
 
@@ -527,20 +771,28 @@ int rfa_pfb_process(rfa_pfb *p, const void *in, size_t n_samples, float *out_re,
     if (!in || (uintptr_t)in % sb != 0) return pfail(p, RFA_ERR_INVALID, "input pointer null or misaligned");
     if (n_samples > (size_t)1 << 40) return pfail(p, RFA_ERR_INVALID, "n_samples too large");
     const long long S = (long long)n_samples;
+    if (p->rational && p->in_done + S >= (long long)1 << 53) return pfail(p, RFA_ERR_INVALID, "stream longer than 2^53 samples");
     const long long n = pfb_outputs(p, S);
     if ((size_t)n > channel_stride) return pfail(p, RFA_ERR_SIZE, "channel_stride smaller than the output count");
     if (n > 0 && (!out_re || !out_im)) return RFA_ERR_INVALID;
-    PfbLaunch a{};
+    PfbRatLaunch b{};
+    PfbLaunch &a = b.a;
     a.raw = in;
     a.S = S;
     a.hist = p->d_hist[p->cur];
     a.new_hist = p->d_hist[p->cur ^ 1];
     a.taps = p->d_taps;
-    a.T = p->T;
+    a.T = p->Th;
     a.M = p->M;
     a.D = p->D;
-    pfb_plan_tile(a);
-    a.n0 = p->in_done / p->D;
+    b.L = p->L;
+    if (p->rational) {
+        pfb_plan_rational(b);
+        a.n0 = pfb_rational_count(p->in_done, p->L, p->D);
+    } else {
+        pfb_plan_tile(a);
+        a.n0 = p->in_done / p->D;
+    }
     a.in0 = p->in_done;
     a.n_out = n;
     a.tw = p->d_tw;
@@ -554,7 +806,14 @@ int rfa_pfb_process(rfa_pfb *p, const void *in, size_t n_samples, float *out_re,
     if ((n + a.NT - 1) / a.NT > (long long)INT32_MAX) return pfail(p, RFA_ERR_INVALID, "call too large for one grid");
     PHIP(p, hipSetDevice(p->device));
     hipError_t e = hipSuccess;
-    switch (p->fmt) {
+    if (p->rational) {
+        switch (p->fmt) {
+        case RFA_IN_S8: e = pfb_rational_launch<RFA_IN_S8>(b, p->stream); break;
+        case RFA_IN_U8: e = pfb_rational_launch<RFA_IN_U8>(b, p->stream); break;
+        case RFA_IN_S16LE: e = pfb_rational_launch<RFA_IN_S16LE>(b, p->stream); break;
+        default: e = pfb_rational_launch<RFA_IN_F32_INTERLEAVED>(b, p->stream); break;
+        }
+    } else switch (p->fmt) {
     case RFA_IN_S8: e = pfb_launch<RFA_IN_S8>(a, p->stream); break;
     case RFA_IN_U8: e = pfb_launch<RFA_IN_U8>(a, p->stream); break;
     case RFA_IN_S16LE: e = pfb_launch<RFA_IN_S16LE>(a, p->stream); break;
@@ -612,7 +871,7 @@ int rfa_pfb_process_host(rfa_pfb *p, const void *in, size_t n_samples, float *ou
 int rfa_pfb_reset(rfa_pfb *p) {
     if (!p) return RFA_ERR_INVALID;
     PHIP(p, hipSetDevice(p->device));
-    const size_t H = (size_t)std::max(1, p->T - 1);
+    const size_t H = (size_t)std::max(1, p->Th - 1);
     PHIP(p, hipMemsetAsync(p->d_hist[p->cur], 0, 2 * H * sizeof(float), p->stream));
     PHIP(p, hipStreamSynchronize(p->stream));
     p->in_done = 0;

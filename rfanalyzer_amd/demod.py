@@ -37,6 +37,7 @@ for a cost that does not grow with the channel count; ``RasterReceiverBank`` cha
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 
@@ -1025,6 +1026,7 @@ class Channelizer:
         self._h = None
         self.fmt = FORMATS[input_format]
         self.n_channels = int(n_channels)
+        self.interpolation = 1
         self.decimation = int(decimation)
         self._stream = None
         taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
@@ -1034,6 +1036,71 @@ class Channelizer:
                    "rfa_pfb_create")
         self._h = h
         self._n_selected = self.n_channels
+
+    @classmethod
+    def rational(cls, input_format: str, n_channels: int, interpolation: int, decimation: int, taps, device: int = 0):
+        """The rational-rate channelizer (``rfa_pfb_create_rational``): the same raster at
+        ``interpolation / decimation`` = L / D times the input rate, 1 <= L <= D <= L * M, gcd 1,
+        L <= 64; ``taps`` is the prototype at L times the input rate, up to 16 * M * L taps.  Output
+        n has phase (n * D) mod L and newest sample floor(n * D / L); after c samples ceil(c * L / D)
+        outputs exist.  L = 1 keeps that convention (m_n = n * D), which is not the plain
+        constructor's n * D + D - 1."""
+        if input_format not in FORMATS:
+            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
+        self = cls.__new__(cls)
+        self._h = None
+        self.fmt = FORMATS[input_format]
+        self.n_channels = int(n_channels)
+        self.interpolation = int(interpolation)
+        self.decimation = int(decimation)
+        self._stream = None
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        h = _lib._h()
+        _lib.check(_lib.lib().rfa_pfb_create_rational(device, self.fmt, self.n_channels, self.interpolation,
+                                                      self.decimation, taps.ctypes.data_as(_lib._fp), taps.size,
+                                                      ctypes.byref(h)), "rfa_pfb_create_rational")
+        self._h = h
+        self._n_selected = self.n_channels
+        return self
+
+    @staticmethod
+    def raster_ratio(sample_rate: int, spacing_hz: int, output_rate: int) -> tuple[int, int, int]:
+        """(M, L, D) of ``for_raster_resampled``: M = sample_rate / spacing_hz, L / D = output_rate /
+        sample_rate in lowest terms; ``ValueError`` where ``rfa_pfb_create_rational`` would refuse them.
+        Host only."""
+        sample_rate, spacing_hz, output_rate = int(sample_rate), int(spacing_hz), int(output_rate)
+        if sample_rate <= 0 or spacing_hz <= 0 or output_rate <= 0:
+            raise ValueError("rates and spacing must be positive")
+        if sample_rate % spacing_hz:
+            raise ValueError("sample_rate must be a whole multiple of spacing_hz")
+        g = math.gcd(sample_rate, output_rate)
+        M, L, D = sample_rate // spacing_hz, output_rate // g, sample_rate // g
+        if L > D:
+            raise ValueError("output_rate above sample_rate")
+        if L > _lib.RFA_PFB_MAX_INTERPOLATION:
+            raise ValueError(f"interpolation {L} above {_lib.RFA_PFB_MAX_INTERPOLATION}")
+        if D > L * M:
+            raise ValueError("output_rate below spacing_hz")
+        if not _lib.lib().rfa_pfb_supported(M):
+            raise ValueError(f"{M} channels: not 2^a 3^b 5^c within 8 ... 4096")
+        return M, L, D
+
+    @classmethod
+    def for_raster_resampled(cls, input_format: str, sample_rate: int, spacing_hz: int, output_rate: int,
+                             device: int = 0):
+        """The channelizer of a raster at any source rate: ``sample_rate / spacing_hz`` channels (a
+        whole number), each at ``output_rate`` = sample_rate * L / D in lowest terms, with the
+        ``for_raster`` design moved to the interpolated rate as prototype
+        (``create_low_pass_taps(L, L * sample_rate, 0.375 * spacing, 0.25 * spacing, 60)``, gain L,
+        about 10.9 * M * L taps, so about 10.9 * M per output).  ``ValueError`` where a limit of
+        ``rfa_pfb_create_rational`` fails."""
+        M, L, D = cls.raster_ratio(sample_rate, spacing_hz, output_rate)
+        taps = create_low_pass_taps(L, L * int(sample_rate), 0.375 * int(spacing_hz), 0.25 * int(spacing_hz), 60)
+        if taps is None:
+            raise ValueError("the low-pass design rejected the raster")
+        if taps.size > 16 * M * L:
+            raise ValueError(f"prototype of {taps.size} taps above 16 * {M} * {L}")
+        return cls.rational(input_format, M, L, D, taps, device)
 
     @classmethod
     def for_raster(cls, input_format: str, sample_rate: int, spacing_hz: int, output_rate: int, device: int = 0):
@@ -1119,6 +1186,14 @@ class Channelizer:
                     "rfa_pfb_get_taps")
         return out
 
+    @property
+    def ratio(self) -> tuple[int, int, int]:
+        """(interpolation, decimation, taps per output) as ``rfa_pfb_get_ratio`` reports them:
+        (1, D, T) on an integer handle, (L, D, ceil(T / L)) on a rational one."""
+        v = [ctypes.c_int32(0) for _ in range(3)]
+        self._check(_lib.lib().rfa_pfb_get_ratio(self._h, *[ctypes.byref(x) for x in v]), "rfa_pfb_get_ratio")
+        return v[0].value, v[1].value, v[2].value
+
     def max_outputs(self, n_samples: int) -> int:
         """The exact output count per channel of the next call of ``n_samples``."""
         n = ctypes.c_size_t(0)
@@ -1191,7 +1266,8 @@ class RasterReceiverBank:
     ``DemodulatorBank`` fed the ``Channelizer``'s own output.  Every mode must have the same
     quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``)."""
 
-    def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0):
+    def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0,
+                 resample: bool = False):
         import torch
 
         modes = list(modes)
@@ -1212,8 +1288,9 @@ class RasterReceiverBank:
         self._raw = self._re = self._im = self._audio = None
         try:
             self.demods = DemodulatorBank(modes, device)
-            self.front = Channelizer.for_raster(input_format, self.sample_rate, spacing_hz, self.quadrature_rate,
-                                                device)
+            self._resample = bool(resample)
+            make = Channelizer.for_raster_resampled if self._resample else Channelizer.for_raster
+            self.front = make(input_format, self.sample_rate, spacing_hz, self.quadrature_rate, device)
             self.front.set_channels(channels)
             self.set_stream(None)
         except Exception:
@@ -1250,7 +1327,10 @@ class RasterReceiverBank:
         torch = self._torch
         if self._raw is None or self._raw.numel() < nbytes:
             self._raw = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self._tdev)
-        cap = n // self.front.decimation + 1          # an upper bound of any call of n samples
+        if self._resample:                            # ceil(c1 L / D) - ceil(c0 L / D) <= ceil(n L / D)
+            cap = -(-n * self.front.interpolation // self.front.decimation) + 1
+        else:
+            cap = n // self.front.decimation + 1      # an upper bound of any call of n samples
         if self._re is None or self._re.shape[1] < cap:
             shape = (self.n_channels, cap)
             self._re = torch.empty(shape, dtype=torch.float32, device=self._tdev)
