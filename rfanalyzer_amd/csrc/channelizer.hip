@@ -46,6 +46,8 @@
 
 #pragma clang fp contract(off)
 
+#include "stage_common.h"
+
 namespace {
 
 constexpr int kPfbThreads = 256;
@@ -75,35 +77,14 @@ struct PfbLaunch {
     float *out_re, *out_im;
 };
 
-// One complex input sample, converted as the front end converts it before mixing
-// (mix_raw in ddc.hip); g is call-relative, negative values index the history.
+// One complex input sample, converted by the code the front end converts with before it
+// mixes (raw_to_iq of stage_common.h); g is call-relative, negative values index the history.
 template <int FMT>
 __device__ __forceinline__ float2 pfb_sample(const PfbLaunch &a, long long g) {
     if (g < 0) return float2{a.hist[a.T - 1 + g], a.hist[2 * (a.T - 1) + g]};
-    if constexpr (FMT == RFA_IN_F32_INTERLEAVED) {
-        return static_cast<const float2 *>(a.raw)[g];
-    } else if constexpr (FMT == RFA_IN_S16LE) {
-        const unsigned v = static_cast<const unsigned *>(a.raw)[g];
-        return float2{(float)(short)(v & 0xffffu) / 32768.0f, (float)(short)(v >> 16) / 32768.0f};
-    } else if constexpr (FMT == RFA_IN_S8) {
-        const unsigned v = static_cast<const unsigned short *>(a.raw)[g];
-        return float2{(float)(signed char)(v & 0xffu) / 128.0f, (float)(signed char)(v >> 8) / 128.0f};
-    } else {
-        const unsigned v = static_cast<const unsigned short *>(a.raw)[g];
-        return float2{((float)(v & 0xffu) - 127.4f) / 128.0f, ((float)(v >> 8) - 127.4f) / 128.0f};
-    }
-}
-
-// One staged sample as its own ds_read_b64 (see lds_ld in ddc.hip: a volatile LDS
-// access keeps neighbours from being fused into ds_read2_b64).
-__device__ __forceinline__ float2 pfb_lds_ld(const float2 *p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    const v2f v = *(const volatile __attribute__((address_space(3))) v2f *)(p);
-    return float2{v.x, v.y};
-#else
-    return *p;
-#endif
+    float2 x;
+    raw_to_iq<FMT>(raw_load<FMT>(a.raw, g), x.x, x.y);
+    return x;
 }
 
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return float2{a.x + b.x, a.y + b.y}; }
@@ -201,7 +182,7 @@ __global__ __launch_bounds__(kPfbThreads) void pfb_kernel(PfbLaunch a) {
             const float2 *x = xs + nl * a.D + (a.T - 1);
 #pragma unroll 4
             for (int t = t0; t < a.T; t += a.M) {
-                const float2 v = pfb_lds_ld(x - t);
+                const float2 v = lds_ld(x - t);
                 const float h = hs[t];
                 acc.x = acc.x + h * v.x;
                 acc.y = acc.y + h * v.y;
@@ -350,7 +331,7 @@ __global__ __launch_bounds__(kPfbThreads) void pfb_rational_kernel(PfbRatLaunch 
             const float *g = b.tap_rows ? gs + (by_phase ? t_ph[nl] : nl) * a.T : a.taps + (long long)t_ph[nl] * a.T;
 #pragma unroll 4
             for (int t = t0; t < a.T; t += a.M) {
-                const float2 v = pfb_lds_ld(x - t);
+                const float2 v = lds_ld(x - t);
                 const float h = g[t];
                 acc.x = acc.x + h * v.x;
                 acc.y = acc.y + h * v.y;
@@ -374,41 +355,19 @@ __global__ __launch_bounds__(kPfbThreads) void pfb_rational_kernel(PfbRatLaunch 
 
 int pfb_lds_bytes(const PfbLaunch &a) { return (a.stage + 2 * a.NT * a.Mp) * (int)sizeof(float2); }
 
-template <int FMT>
-hipError_t pfb_rational_prepare() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(pfb_rational_kernel<FMT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
+// kernel: pfb_kernel<FMT> (its record is a PfbLaunch) or pfb_rational_kernel<FMT> (a PfbRatLaunch)
+template <class Rec>
+hipError_t pfb_prepare(void (*kernel)(Rec)) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                kPfbStageBytes + 2 * (kPfbTilePoints + kPfbMaxTimes) * (int)sizeof(float2));
 }
 
-template <int FMT>
-hipError_t pfb_rational_launch(const PfbRatLaunch &b, hipStream_t st) {
-    if (b.a.n_out > 0) {
-        const long long blocks = (b.a.n_out + b.a.NT - 1) / b.a.NT;
-        hipLaunchKernelGGL(pfb_rational_kernel<FMT>, dim3((unsigned)blocks), dim3(kPfbThreads), pfb_lds_bytes(b.a), st, b);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    if (b.a.T > 1) {
-        hipLaunchKernelGGL(pfb_hist_kernel<FMT>, dim3((b.a.T - 1 + kPfbThreads - 1) / kPfbThreads), dim3(kPfbThreads), 0,
-                           st, b.a);
-        return hipGetLastError();
-    }
-    return hipSuccess;
-}
-
-template <int FMT>
-hipError_t pfb_prepare() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(pfb_kernel<FMT>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               kPfbStageBytes + 2 * (kPfbTilePoints + kPfbMaxTimes) * (int)sizeof(float2));
-}
-
-template <int FMT>
-hipError_t pfb_launch(const PfbLaunch &a, hipStream_t st) {
+// The fold + DFT kernel on its record, then the history kernel on the record's PfbLaunch a.
+template <int FMT, class Rec>
+hipError_t pfb_launch(void (*kernel)(Rec), const Rec &rec, const PfbLaunch &a, hipStream_t st) {
     if (a.n_out > 0) {
         const long long blocks = (a.n_out + a.NT - 1) / a.NT;
-        hipLaunchKernelGGL(pfb_kernel<FMT>, dim3((unsigned)blocks), dim3(kPfbThreads), pfb_lds_bytes(a), st, a);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kPfbThreads), pfb_lds_bytes(a), st, rec);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -497,20 +456,9 @@ long long pfb_gcd(long long a, long long b) {
 // Outputs due once c samples are consumed: ceil(c * L / D); c < 2^53 and L <= 64 keep the product in range.
 long long pfb_rational_count(long long c, int L, int D) { return (c * L + D - 1) / D; }
 
-size_t pfb_sample_bytes(int fmt) {
-    switch (fmt) {
-    case RFA_IN_S8:
-    case RFA_IN_U8: return 2;
-    case RFA_IN_S16LE: return 4;
-    case RFA_IN_F32_INTERLEAVED: return 8;
-    default: return 0;
-    }
-}
-
 }  // namespace
 
-struct rfa_pfb {
-    int device = 0;
+struct rfa_pfb : StageCore {
     int fmt = 0;
     int M = 0, D = 0, T = 0;
     int L = 1;                          // interpolation; above 1 only on a rational handle
@@ -520,9 +468,6 @@ struct rfa_pfb {
     std::vector<float> gp;              // rational: the device table gp[L][Tp], gp[p][t] = taps[p + t * L]
     std::vector<int> radix, tw_off;
     std::vector<int32_t> channels;      // slot -> channel
-    hipStream_t stream = nullptr;       // where work is enqueued (own_stream or the caller's)
-    hipStream_t own_stream = nullptr;   // created by the handle; set once rfa_pfb_set_stream is used
-    std::string err;
     long long in_done = 0;              // samples consumed since creation or reset
     float *d_taps = nullptr;
     float2 *d_tw = nullptr;
@@ -537,17 +482,6 @@ struct rfa_pfb {
 };
 
 namespace {
-
-int pfail(rfa_pfb *p, int code, const std::string &msg) {
-    if (p) p->err = msg;
-    return code;
-}
-
-#define PHIP(p, expr)                                                                  \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess) return pfail((p), RFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 long long pfb_outputs(const rfa_pfb *p, long long S) {
     if (p->rational) return pfb_rational_count(p->in_done + S, p->L, p->D) - pfb_rational_count(p->in_done, p->L, p->D);
@@ -564,35 +498,51 @@ int pfb_upload(rfa_pfb *p) {
         hipMalloc(&p->d_chan, (size_t)p->M * sizeof(int)) != hipSuccess ||
         hipMalloc(&p->d_hist[0], 2 * H * sizeof(float)) != hipSuccess ||
         hipMalloc(&p->d_hist[1], 2 * H * sizeof(float)) != hipSuccess)
-        return pfail(p, RFA_ERR_NOMEM, "hipMalloc channelizer tables");
-    PHIP(p, hipMemcpyAsync(p->d_taps, dtaps.data(), dtaps.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
+        return stage_fail(p, RFA_ERR_NOMEM, "hipMalloc channelizer tables");
+    STAGE_HIP(p, hipMemcpyAsync(p->d_taps, dtaps.data(), dtaps.size() * sizeof(float), hipMemcpyHostToDevice, p->stream));
     if (!tw.empty())
-        PHIP(p, hipMemcpyAsync(p->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, p->stream));
-    PHIP(p, hipMemcpyAsync(p->d_chan, p->channels.data(), p->channels.size() * sizeof(int), hipMemcpyHostToDevice,
+        STAGE_HIP(p, hipMemcpyAsync(p->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, p->stream));
+    STAGE_HIP(p, hipMemcpyAsync(p->d_chan, p->channels.data(), p->channels.size() * sizeof(int), hipMemcpyHostToDevice,
                            p->stream));
-    PHIP(p, hipMemsetAsync(p->d_hist[0], 0, 2 * H * sizeof(float), p->stream));
-    PHIP(p, hipMemsetAsync(p->d_hist[1], 0, 2 * H * sizeof(float), p->stream));
-    PHIP(p, hipStreamSynchronize(p->stream));
-    PHIP(p, pfb_prepare<RFA_IN_S8>());
-    PHIP(p, pfb_prepare<RFA_IN_U8>());
-    PHIP(p, pfb_prepare<RFA_IN_S16LE>());
-    PHIP(p, pfb_prepare<RFA_IN_F32_INTERLEAVED>());
-    if (p->rational) {
-        PHIP(p, pfb_rational_prepare<RFA_IN_S8>());
-        PHIP(p, pfb_rational_prepare<RFA_IN_U8>());
-        PHIP(p, pfb_rational_prepare<RFA_IN_S16LE>());
-        PHIP(p, pfb_rational_prepare<RFA_IN_F32_INTERLEAVED>());
+    STAGE_HIP(p, hipMemsetAsync(p->d_hist[0], 0, 2 * H * sizeof(float), p->stream));
+    STAGE_HIP(p, hipMemsetAsync(p->d_hist[1], 0, 2 * H * sizeof(float), p->stream));
+    STAGE_HIP(p, hipStreamSynchronize(p->stream));
+    for (int fmt : {RFA_IN_S8, RFA_IN_U8, RFA_IN_S16LE, RFA_IN_F32_INTERLEAVED}) {
+        STAGE_HIP(p, stage_dispatch_format(fmt, [](auto f) { return pfb_prepare(pfb_kernel<decltype(f)::value>); }));
+        if (p->rational)
+            STAGE_HIP(p, stage_dispatch_format(
+                             fmt, [](auto f) { return pfb_prepare(pfb_rational_kernel<decltype(f)::value>); }));
     }
     return RFA_OK;
 }
 
-// The device part of both create entries: stream, tables, history.
-int pfb_finish_create(rfa_pfb *p, rfa_pfb **out) {
-    int rc = RFA_OK;
-    if (hipSetDevice(p->device) != hipSuccess || hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess)
-        rc = RFA_ERR_HIP;
-    else
-        rc = pfb_upload(p);
+// Both create entries after their own argument checks: the handle for the raster M with the
+// prototype `taps` at L times the input rate (rational: the L / D convention, L = 1 included),
+// its stream, tables and history.
+int pfb_create(int device, int input_format, int32_t M, int32_t L, int32_t D, bool rational, const float *taps,
+               int32_t num_taps, rfa_pfb **out) {
+    if (!rfa_pfb_supported(M)) return RFA_ERR_UNSUPPORTED;
+    int rc = stage_check_device(device);
+    if (rc != RFA_OK) return rc;
+    rfa_pfb *p = new (std::nothrow) rfa_pfb();
+    if (!p) return RFA_ERR_NOMEM;
+    p->fmt = input_format;
+    p->M = M;
+    p->L = L;
+    p->D = D;
+    p->T = num_taps;
+    p->Th = (num_taps + L - 1) / L;
+    p->rational = rational;
+    p->taps.assign(taps, taps + num_taps);
+    if (rational) {
+        p->gp.assign((size_t)L * p->Th, 0.0f);
+        for (int s = 0; s < num_taps; s++) p->gp[(size_t)(s % L) * p->Th + s / L] = taps[s];
+    }
+    p->radix = pfb_radices(M);
+    p->channels.resize(M);
+    for (int k = 0; k < M; k++) p->channels[k] = k;
+    rc = stage_open(p, device);
+    if (rc == RFA_OK) rc = pfb_upload(p);
     if (rc != RFA_OK) {
         rfa_pfb_destroy(p);
         return rc;
@@ -611,61 +561,25 @@ int rfa_pfb_create(int device, int input_format, int32_t n_channels, int32_t dec
                    int32_t num_taps, rfa_pfb **out) {
     if (!out) return RFA_ERR_INVALID;
     *out = nullptr;
-    if (pfb_sample_bytes(input_format) == 0 || n_channels < 1 || decimation < 1 || !taps || num_taps < 1)
+    if (stage_sample_bytes(input_format) == 0 || n_channels < 1 || decimation < 1 || !taps || num_taps < 1)
         return RFA_ERR_INVALID;
     if (decimation > n_channels || (long long)num_taps > (long long)RFA_PFB_MAX_PHASES * n_channels)
         return RFA_ERR_INVALID;
-    if (!rfa_pfb_supported(n_channels)) return RFA_ERR_UNSUPPORTED;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
-    if (device < 0 || device >= count) return RFA_ERR_INVALID;
-    rfa_pfb *p = new (std::nothrow) rfa_pfb();
-    if (!p) return RFA_ERR_NOMEM;
-    p->device = device;
-    p->fmt = input_format;
-    p->M = n_channels;
-    p->D = decimation;
-    p->T = num_taps;
-    p->Th = num_taps;
-    p->taps.assign(taps, taps + num_taps);
-    p->radix = pfb_radices(n_channels);
-    p->channels.resize(n_channels);
-    for (int k = 0; k < n_channels; k++) p->channels[k] = k;
-    return pfb_finish_create(p, out);
+    return pfb_create(device, input_format, n_channels, 1, decimation, false, taps, num_taps, out);
 }
 
 int rfa_pfb_create_rational(int device, int input_format, int32_t n_channels, int32_t interpolation, int32_t decimation,
                             const float *taps, int32_t num_taps, rfa_pfb **out) {
     if (!out) return RFA_ERR_INVALID;
     *out = nullptr;
-    if (pfb_sample_bytes(input_format) == 0 || n_channels < 1 || interpolation < 1 || decimation < 1 || !taps ||
+    if (stage_sample_bytes(input_format) == 0 || n_channels < 1 || interpolation < 1 || decimation < 1 || !taps ||
         num_taps < 1)
         return RFA_ERR_INVALID;
     if (interpolation > RFA_PFB_MAX_INTERPOLATION || interpolation > decimation ||
         (long long)decimation > (long long)interpolation * n_channels || pfb_gcd(interpolation, decimation) != 1 ||
         (long long)num_taps > (long long)RFA_PFB_MAX_PHASES * n_channels * interpolation)
         return RFA_ERR_INVALID;
-    if (!rfa_pfb_supported(n_channels)) return RFA_ERR_UNSUPPORTED;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
-    if (device < 0 || device >= count) return RFA_ERR_INVALID;
-    rfa_pfb *p = new (std::nothrow) rfa_pfb();
-    if (!p) return RFA_ERR_NOMEM;
-    p->device = device;
-    p->fmt = input_format;
-    p->M = n_channels;
-    p->L = interpolation;
-    p->D = decimation;
-    p->T = num_taps;
-    p->Th = (num_taps + interpolation - 1) / interpolation;
-    p->rational = true;
-    p->taps.assign(taps, taps + num_taps);
-    p->gp.assign((size_t)p->L * p->Th, 0.0f);
-    for (int s = 0; s < num_taps; s++) p->gp[(size_t)(s % p->L) * p->Th + s / p->L] = taps[s];
-    p->radix = pfb_radices(n_channels);
-    p->channels.resize(n_channels);
-    for (int k = 0; k < n_channels; k++) p->channels[k] = k;
-    return pfb_finish_create(p, out);
+    return pfb_create(device, input_format, n_channels, interpolation, decimation, true, taps, num_taps, out);
 }
 
 int rfa_pfb_get_ratio(const rfa_pfb *p, int32_t *interpolation, int32_t *decimation, int32_t *taps_per_output) {
@@ -689,18 +603,15 @@ int rfa_pfb_rational_outputs(int32_t interpolation, int32_t decimation, uint64_t
 
 int rfa_pfb_destroy(rfa_pfb *p) {
     if (!p) return RFA_ERR_INVALID;
-    hipSetDevice(p->device);
-    if (p->stream) hipStreamSynchronize(p->stream);
+    stage_close_stream(p);
     for (void *q : {(void *)p->d_taps, (void *)p->d_tw, (void *)p->d_chan, (void *)p->d_hist[0], (void *)p->d_hist[1],
                     p->d_in, (void *)p->d_out})
         if (q) hipFree(q);
-    hipStream_t own = p->own_stream ? p->own_stream : p->stream;
-    if (own) hipStreamDestroy(own);
     delete p;
     return RFA_OK;
 }
 
-const char *rfa_pfb_last_error(const rfa_pfb *p) { return p ? p->err.c_str() : "null handle"; }
+const char *rfa_pfb_last_error(const rfa_pfb *p) { return stage_last_error(p); }
 
 int rfa_pfb_get_plan(const rfa_pfb *p, int32_t *n_channels, int32_t *decimation, int32_t *num_taps, int32_t *radices,
                      int32_t cap, int32_t *count) {
@@ -728,7 +639,7 @@ int rfa_pfb_get_taps(const rfa_pfb *p, float *taps, size_t capacity, int32_t *nu
 
 int rfa_pfb_set_channels(rfa_pfb *p, const int32_t *channels, int32_t count) {
     if (!p) return RFA_ERR_INVALID;
-    if (count < 0 || count > p->M) return pfail(p, RFA_ERR_INVALID, "channel count outside 0 .. n_channels");
+    if (count < 0 || count > p->M) return stage_fail(p, RFA_ERR_INVALID, "channel count outside 0 .. n_channels");
     std::vector<int32_t> ch;
     if (!channels || count == 0) {
         ch.resize(p->M);
@@ -736,12 +647,12 @@ int rfa_pfb_set_channels(rfa_pfb *p, const int32_t *channels, int32_t count) {
     } else {
         ch.assign(channels, channels + count);
         for (int32_t c : ch)
-            if (c < 0 || c >= p->M) return pfail(p, RFA_ERR_INVALID, "channel outside 0 .. n_channels - 1");
+            if (c < 0 || c >= p->M) return stage_fail(p, RFA_ERR_INVALID, "channel outside 0 .. n_channels - 1");
     }
-    PHIP(p, hipSetDevice(p->device));
-    PHIP(p, hipStreamSynchronize(p->stream));     // an enqueued call still reads the old list
-    PHIP(p, hipMemcpyAsync(p->d_chan, ch.data(), ch.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
-    PHIP(p, hipStreamSynchronize(p->stream));
+    STAGE_HIP(p, hipSetDevice(p->device));
+    STAGE_HIP(p, hipStreamSynchronize(p->stream));     // an enqueued call still reads the old list
+    STAGE_HIP(p, hipMemcpyAsync(p->d_chan, ch.data(), ch.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    STAGE_HIP(p, hipStreamSynchronize(p->stream));
     p->channels = std::move(ch);
     return RFA_OK;
 }
@@ -767,13 +678,13 @@ int rfa_pfb_process(rfa_pfb *p, const void *in, size_t n_samples, float *out_re,
     if (!p || !n_out) return RFA_ERR_INVALID;
     *n_out = 0;
     if (n_samples == 0) return RFA_OK;
-    const size_t sb = pfb_sample_bytes(p->fmt);
-    if (!in || (uintptr_t)in % sb != 0) return pfail(p, RFA_ERR_INVALID, "input pointer null or misaligned");
-    if (n_samples > (size_t)1 << 40) return pfail(p, RFA_ERR_INVALID, "n_samples too large");
+    const size_t sb = stage_sample_bytes(p->fmt);
+    if (!in || (uintptr_t)in % sb != 0) return stage_fail(p, RFA_ERR_INVALID, "input pointer null or misaligned");
+    if (n_samples > (size_t)1 << 40) return stage_fail(p, RFA_ERR_INVALID, "n_samples too large");
     const long long S = (long long)n_samples;
-    if (p->rational && p->in_done + S >= (long long)1 << 53) return pfail(p, RFA_ERR_INVALID, "stream longer than 2^53 samples");
+    if (p->rational && p->in_done + S >= (long long)1 << 53) return stage_fail(p, RFA_ERR_INVALID, "stream longer than 2^53 samples");
     const long long n = pfb_outputs(p, S);
-    if ((size_t)n > channel_stride) return pfail(p, RFA_ERR_SIZE, "channel_stride smaller than the output count");
+    if ((size_t)n > channel_stride) return stage_fail(p, RFA_ERR_SIZE, "channel_stride smaller than the output count");
     if (n > 0 && (!out_re || !out_im)) return RFA_ERR_INVALID;
     PfbRatLaunch b{};
     PfbLaunch &a = b.a;
@@ -803,23 +714,14 @@ int rfa_pfb_process(rfa_pfb *p, const void *in, size_t n_samples, float *out_re,
     a.stride = (long long)channel_stride;
     a.out_re = out_re;
     a.out_im = out_im;
-    if ((n + a.NT - 1) / a.NT > (long long)INT32_MAX) return pfail(p, RFA_ERR_INVALID, "call too large for one grid");
-    PHIP(p, hipSetDevice(p->device));
-    hipError_t e = hipSuccess;
-    if (p->rational) {
-        switch (p->fmt) {
-        case RFA_IN_S8: e = pfb_rational_launch<RFA_IN_S8>(b, p->stream); break;
-        case RFA_IN_U8: e = pfb_rational_launch<RFA_IN_U8>(b, p->stream); break;
-        case RFA_IN_S16LE: e = pfb_rational_launch<RFA_IN_S16LE>(b, p->stream); break;
-        default: e = pfb_rational_launch<RFA_IN_F32_INTERLEAVED>(b, p->stream); break;
-        }
-    } else switch (p->fmt) {
-    case RFA_IN_S8: e = pfb_launch<RFA_IN_S8>(a, p->stream); break;
-    case RFA_IN_U8: e = pfb_launch<RFA_IN_U8>(a, p->stream); break;
-    case RFA_IN_S16LE: e = pfb_launch<RFA_IN_S16LE>(a, p->stream); break;
-    default: e = pfb_launch<RFA_IN_F32_INTERLEAVED>(a, p->stream); break;
-    }
-    if (e != hipSuccess) return pfail(p, RFA_ERR_HIP, std::string("channelizer launch: ") + hipGetErrorString(e));
+    if ((n + a.NT - 1) / a.NT > (long long)INT32_MAX) return stage_fail(p, RFA_ERR_INVALID, "call too large for one grid");
+    STAGE_HIP(p, hipSetDevice(p->device));
+    const hipError_t e = stage_dispatch_format(p->fmt, [&](auto f) {
+        constexpr int FMT = decltype(f)::value;
+        return p->rational ? pfb_launch<FMT>(pfb_rational_kernel<FMT>, b, a, p->stream)
+                           : pfb_launch<FMT>(pfb_kernel<FMT>, a, a, p->stream);
+    });
+    if (e != hipSuccess) return stage_fail(p, RFA_ERR_HIP, std::string("channelizer launch: ") + hipGetErrorString(e));
     if (a.T > 1) p->cur ^= 1;
     p->in_done += S;
     *n_out = (size_t)n;
@@ -831,74 +733,46 @@ int rfa_pfb_process_host(rfa_pfb *p, const void *in, size_t n_samples, float *ou
     if (!p || !n_out || (n_samples && !in)) return RFA_ERR_INVALID;
     *n_out = 0;
     if (n_samples == 0) return RFA_OK;
-    if (n_samples > (size_t)1 << 40) return pfail(p, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples > (size_t)1 << 40) return stage_fail(p, RFA_ERR_INVALID, "n_samples too large");
     const size_t K = p->channels.size();
-    const size_t bytes = n_samples * pfb_sample_bytes(p->fmt);
+    const size_t bytes = n_samples * stage_sample_bytes(p->fmt);
     const size_t most = (size_t)pfb_outputs(p, (long long)n_samples);
-    if (most > channel_stride) return pfail(p, RFA_ERR_SIZE, "channel_stride smaller than the output count");
+    if (most > channel_stride) return stage_fail(p, RFA_ERR_SIZE, "channel_stride smaller than the output count");
     if (most > 0 && (!out_re || !out_im)) return RFA_ERR_INVALID;
-    PHIP(p, hipSetDevice(p->device));
-    if (bytes > p->d_in_cap) {
-        if (p->d_in) hipFree(p->d_in);
-        p->d_in = nullptr;
-        p->d_in_cap = 0;
-        if (hipMalloc(&p->d_in, bytes) != hipSuccess) return pfail(p, RFA_ERR_NOMEM, "hipMalloc input staging");
-        p->d_in_cap = bytes;
-    }
+    STAGE_HIP(p, hipSetDevice(p->device));
     const size_t pitch = most + 1;
-    if (2 * K * pitch > p->d_out_cap) {
-        if (p->d_out) hipFree(p->d_out);
-        p->d_out = nullptr;
-        p->d_out_cap = 0;
-        if (hipMalloc(&p->d_out, 2 * K * pitch * sizeof(float)) != hipSuccess) return pfail(p, RFA_ERR_NOMEM, "hipMalloc output staging");
-        p->d_out_cap = 2 * K * pitch;
-    }
-    PHIP(p, hipMemcpyAsync(p->d_in, in, bytes, hipMemcpyHostToDevice, p->stream));
+    int rc = stage_grow(p, p->d_in, p->d_in_cap, bytes, "input staging");
+    if (rc == RFA_OK) rc = stage_grow(p, p->d_out, p->d_out_cap, 2 * K * pitch, "output staging");
+    if (rc != RFA_OK) return rc;
+    STAGE_HIP(p, hipMemcpyAsync(p->d_in, in, bytes, hipMemcpyHostToDevice, p->stream));
     size_t n = 0;
-    const int rc = rfa_pfb_process(p, p->d_in, n_samples, p->d_out, p->d_out + K * pitch, pitch, &n);
+    rc = rfa_pfb_process(p, p->d_in, n_samples, p->d_out, p->d_out + K * pitch, pitch, &n);
     if (rc != RFA_OK) return rc;
     if (n) {
-        PHIP(p, hipMemcpy2DAsync(out_re, channel_stride * sizeof(float), p->d_out, pitch * sizeof(float),
+        STAGE_HIP(p, hipMemcpy2DAsync(out_re, channel_stride * sizeof(float), p->d_out, pitch * sizeof(float),
                                  n * sizeof(float), K, hipMemcpyDeviceToHost, p->stream));
-        PHIP(p, hipMemcpy2DAsync(out_im, channel_stride * sizeof(float), p->d_out + K * pitch, pitch * sizeof(float),
+        STAGE_HIP(p, hipMemcpy2DAsync(out_im, channel_stride * sizeof(float), p->d_out + K * pitch, pitch * sizeof(float),
                                  n * sizeof(float), K, hipMemcpyDeviceToHost, p->stream));
     }
-    PHIP(p, hipStreamSynchronize(p->stream));
+    STAGE_HIP(p, hipStreamSynchronize(p->stream));
     *n_out = n;
     return RFA_OK;
 }
 
 int rfa_pfb_reset(rfa_pfb *p) {
     if (!p) return RFA_ERR_INVALID;
-    PHIP(p, hipSetDevice(p->device));
+    STAGE_HIP(p, hipSetDevice(p->device));
     const size_t H = (size_t)std::max(1, p->Th - 1);
-    PHIP(p, hipMemsetAsync(p->d_hist[p->cur], 0, 2 * H * sizeof(float), p->stream));
-    PHIP(p, hipStreamSynchronize(p->stream));
+    STAGE_HIP(p, hipMemsetAsync(p->d_hist[p->cur], 0, 2 * H * sizeof(float), p->stream));
+    STAGE_HIP(p, hipStreamSynchronize(p->stream));
     p->in_done = 0;
     return RFA_OK;
 }
 
-int rfa_pfb_set_stream(rfa_pfb *p, void *stream) {
-    if (!p) return RFA_ERR_INVALID;
-    // the history and the channel list are ordered on the handle's stream: drain it first
-    PHIP(p, hipSetDevice(p->device));
-    PHIP(p, hipStreamSynchronize(p->stream));
-    if (p->own_stream == nullptr) p->own_stream = p->stream;
-    p->stream = stream ? (hipStream_t)stream : p->own_stream;
-    return RFA_OK;
-}
+int rfa_pfb_set_stream(rfa_pfb *p, void *stream) { return stage_set_stream(p, stream); }
 
-int rfa_pfb_get_stream(const rfa_pfb *p, void **stream) {
-    if (!p || !stream) return RFA_ERR_INVALID;
-    *stream = (void *)p->stream;
-    return RFA_OK;
-}
+int rfa_pfb_get_stream(const rfa_pfb *p, void **stream) { return stage_get_stream(p, stream); }
 
-int rfa_pfb_synchronize(rfa_pfb *p) {
-    if (!p) return RFA_ERR_INVALID;
-    PHIP(p, hipSetDevice(p->device));
-    PHIP(p, hipStreamSynchronize(p->stream));
-    return RFA_OK;
-}
+int rfa_pfb_synchronize(rfa_pfb *p) { return stage_synchronize(p); }
 
 }  // extern "C"

@@ -29,6 +29,8 @@
 
 #pragma clang fp contract(off)
 
+#include "stage_common.h"
+
 namespace {
 
 constexpr int kThreads = 256;           // largest workgroup
@@ -64,8 +66,6 @@ struct DdcLaunch {
     float *out_re, *out_im;
 };
 
-template <int FMT> struct RawOf { using type = unsigned; };
-template <> struct RawOf<RFA_IN_F32_INTERLEAVED> { using type = float2; };
 // Four consecutive samples as one load.
 template <int FMT> struct Raw4Of { using type = uint2; };        // 8-bit I,Q x 4
 template <> struct Raw4Of<RFA_IN_S16LE> { using type = uint4; };  // int16 I,Q x 4
@@ -76,32 +76,20 @@ __device__ __forceinline__ unsigned raw4_elem(typename Raw4Of<FMT>::type v, int 
     else return ((e < 2 ? v.x : v.y) >> (16 * (e & 1))) & 0xffffu;
 }
 
-// One complex input sample as stored (I,Q bytes / int16 pair / float pair).
+// One complex input sample as stored (raw_load of stage_common.h).
 template <int FMT>
 __device__ __forceinline__ typename RawOf<FMT>::type load_raw(const DdcLaunch &a, long long g) {
-    if constexpr (FMT == RFA_IN_F32_INTERLEAVED) return static_cast<const float2 *>(a.raw)[g];
-    else if constexpr (FMT == RFA_IN_S16LE) return static_cast<const unsigned *>(a.raw)[g];
-    else return static_cast<const unsigned short *>(a.raw)[g];
+    return raw_load<FMT>(a.raw, g);
 }
 
-// LUT conversion + NCO mix of one raw sample with the table entry (c, s).
+// LUT conversion (raw_to_iq of stage_common.h) + NCO mix of one raw sample with the table entry (c, s).
 template <int FMT>
 __device__ __forceinline__ void mix_raw(typename RawOf<FMT>::type v, float c, float s, float &re, float &im) {
     if constexpr (FMT == RFA_IN_F32_INTERLEAVED) {
-        re = v.x;
-        im = v.y;
+        raw_to_iq<FMT>(v, re, im);
     } else {
         float i, q;
-        if constexpr (FMT == RFA_IN_S16LE) {
-            i = (float)(short)(v & 0xffffu) / 32768.0f;
-            q = (float)(short)(v >> 16) / 32768.0f;
-        } else if constexpr (FMT == RFA_IN_S8) {
-            i = (float)(signed char)(v & 0xffu) / 128.0f;
-            q = (float)(signed char)(v >> 8) / 128.0f;
-        } else {
-            i = ((float)(v & 0xffu) - 127.4f) / 128.0f;
-            q = ((float)(v >> 8) - 127.4f) / 128.0f;
-        }
+        raw_to_iq<FMT>(v, i, q);
         re = i * c - q * s;
         im = q * c + i * s;
     }
@@ -124,21 +112,6 @@ __device__ __forceinline__ int cos_index(const DdcLaunch &a, long long g) {
     if (a.L <= 0) return 0;
     const long long r = ((long long)a.ci + g) % a.L;
     return (int)(r < 0 ? r + a.L : r);
-}
-
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-// One staged (re, im) pair as its own ds_read_b64.  A volatile LDS access keeps
-// the compiler from fusing neighbours into ds_read2_b64, which moves half the
-// bytes per LDS cycle on gfx950 (MI355X_MICROARCH.md, LDS table); the loads
-// still issue back to back with counted waits (measured 3-9 % faster,
-// profiles/r01o/ddc_unfused_lds_reads_ab.txt).
-__device__ __forceinline__ v2f lds_ld(const v2f *p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return *(const volatile __attribute__((address_space(3))) v2f *)(p);
-#else
-    return *p;
-#endif
 }
 
 // One lane per decimated output; blockDim = P rounded up to a wave.  The
@@ -444,13 +417,9 @@ void mixer_table(int fmt, int32_t sr, int32_t cf, std::vector<float> &c, std::ve
 
 }  // namespace
 
-struct rfa_ddc {
-    int device = 0;
+struct rfa_ddc : StageCore {
     int fmt = 0;
     int32_t sample_rate = 0, out_rate = 0;
-    hipStream_t stream = nullptr;       // where work is enqueued (own_stream or the caller's)
-    hipStream_t own_stream = nullptr;   // created by the handle; set once rfa_ddc_set_stream is used
-    std::string err;
     // mixer (IQConverter state)
     bool mixer_valid = false;
     int32_t cos_freq = 0;
@@ -481,27 +450,6 @@ struct rfa_ddc {
 
 namespace {
 
-int dfail(rfa_ddc *d, int code, const std::string &msg) {
-    if (d) d->err = msg;
-    return code;
-}
-
-#define DHIP(d, expr)                                                                  \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess) return dfail((d), RFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-size_t ddc_sample_bytes(int fmt) {
-    switch (fmt) {
-    case RFA_IN_S8:
-    case RFA_IN_U8: return 2;
-    case RFA_IN_S16LE: return 4;
-    case RFA_IN_F32_INTERLEAVED: return 8;
-    default: return 0;
-    }
-}
-
 // (Re)build the filter for the current rates with a zeroed delay line:
 // mode 0 Decimator.java:177-181 (decimationCounter 1: first output at input
 // D-1), mode 1 Resampler.kt:102-110 + RationalResampler.kt:27-60 (ctr 0).
@@ -515,18 +463,18 @@ int rebuild_filter(rfa_ddc *d) {
     } else if (d->mode == 0) {
         D = d->sample_rate / d->out_rate;
         if (!design_low_pass(1.0f, (float)d->sample_rate, d->out_rate * 0.75f, d->out_rate * 0.25f, 60.0f, 0, taps))
-            return dfail(d, RFA_ERR_INVALID, "low-pass design rejected the rates (createLowPassTaps returns null)");
-        if (D < 1) return dfail(d, RFA_ERR_INVALID, "output rate above input rate");
+            return stage_fail(d, RFA_ERR_INVALID, "low-pass design rejected the rates (createLowPassTaps returns null)");
+        if (D < 1) return stage_fail(d, RFA_ERR_INVALID, "output rate above input rate");
         T = (int)taps.size();
     } else {
         limit_denominator(d->out_rate, d->sample_rate, 10000, I, D);
         const int g = gcd_i(I, D);
         I /= g;
         D /= g;
-        if (I < 1 || D < 1) return dfail(d, RFA_ERR_INVALID, "rate ratio");
-        if (I > D) return dfail(d, RFA_ERR_UNSUPPORTED, "upsampling (the reference resampler only guarantees downsampling)");
+        if (I < 1 || D < 1) return stage_fail(d, RFA_ERR_INVALID, "rate ratio");
+        if (I > D) return stage_fail(d, RFA_ERR_UNSUPPORTED, "upsampling (the reference resampler only guarantees downsampling)");
         design_resampler_taps(I, D, 0.4f, 500, proto);
-        if (proto.empty()) return dfail(d, RFA_ERR_INVALID, "resampler design rejected the rates");
+        if (proto.empty()) return stage_fail(d, RFA_ERR_INVALID, "resampler design rejected the rates");
         while (proto.size() % I) proto.push_back(0.0f);
         T = (int)(proto.size() / I);
         taps.resize(proto.size());
@@ -541,14 +489,14 @@ int rebuild_filter(rfa_ddc *d) {
         d->d_taps = nullptr;
         d->taps_cap = 0;
         const size_t cap = std::max(bank, H);
-        if (hipMalloc(&d->d_taps, cap * sizeof(float)) != hipSuccess) return dfail(d, RFA_ERR_NOMEM, "hipMalloc taps");
+        if (hipMalloc(&d->d_taps, cap * sizeof(float)) != hipSuccess) return stage_fail(d, RFA_ERR_NOMEM, "hipMalloc taps");
         for (float *&h : d->d_hist)
-            if (hipMalloc(&h, 2 * cap * sizeof(float)) != hipSuccess) return dfail(d, RFA_ERR_NOMEM, "hipMalloc history");
+            if (hipMalloc(&h, 2 * cap * sizeof(float)) != hipSuccess) return stage_fail(d, RFA_ERR_NOMEM, "hipMalloc history");
         d->taps_cap = cap;
     }
-    DHIP(d, hipMemcpyAsync(d->d_taps, taps.data(), bank * sizeof(float), hipMemcpyHostToDevice, d->stream));
-    DHIP(d, hipMemsetAsync(d->d_hist[0], 0, 2 * H * sizeof(float), d->stream));
-    DHIP(d, hipStreamSynchronize(d->stream));
+    STAGE_HIP(d, hipMemcpyAsync(d->d_taps, taps.data(), bank * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    STAGE_HIP(d, hipMemsetAsync(d->d_hist[0], 0, 2 * H * sizeof(float), d->stream));
+    STAGE_HIP(d, hipStreamSynchronize(d->stream));
     d->taps = std::move(taps);
     d->proto = std::move(proto);
     d->I = I;
@@ -607,11 +555,6 @@ void plan_tiles(DdcLaunch &a) {
     a.lds_bytes = (int)lds_of(a.P, a.KC);
 }
 
-template <int FMT>
-hipError_t dispatch(const DdcLaunch &a, hipStream_t st) {
-    return launch_ddc<FMT>(a, st);
-}
-
 }  // namespace
 
 extern "C" {
@@ -634,13 +577,11 @@ static int ddc_create(int mode, int device, int input_format, int32_t sample_rat
                       rfa_ddc **out, const float *fir_taps = nullptr, int fir_ntaps = 0, int fir_decimation = 1) {
     if (!out) return RFA_ERR_INVALID;
     *out = nullptr;
-    if (ddc_sample_bytes(input_format) == 0 || sample_rate <= 0 || output_sample_rate <= 0) return RFA_ERR_INVALID;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
-    if (device < 0 || device >= count) return RFA_ERR_INVALID;
+    if (stage_sample_bytes(input_format) == 0 || sample_rate <= 0 || output_sample_rate <= 0) return RFA_ERR_INVALID;
+    int rc = stage_check_device(device);
+    if (rc != RFA_OK) return rc;
     rfa_ddc *d = new (std::nothrow) rfa_ddc();
     if (!d) return RFA_ERR_NOMEM;
-    d->device = device;
     d->mode = mode;
     d->fmt = input_format;
     d->sample_rate = sample_rate;
@@ -649,11 +590,8 @@ static int ddc_create(int mode, int device, int input_format, int32_t sample_rat
         d->fir_taps.assign(fir_taps, fir_taps + fir_ntaps);
         d->fir_decimation = fir_decimation;
     }
-    int rc = RFA_OK;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess)
-        rc = RFA_ERR_HIP;
-    else
-        rc = rebuild_filter(d);
+    rc = stage_open(d, device);
+    if (rc == RFA_OK) rc = rebuild_filter(d);
     if (rc != RFA_OK) {
         rfa_ddc_destroy(d);
         return rc;
@@ -680,15 +618,7 @@ int rfa_ddc_create_fir(int device, int input_format, int32_t sample_rate, const 
                       decimation);
 }
 
-int rfa_ddc_set_stream(rfa_ddc *d, void *stream) {
-    if (!d) return RFA_ERR_INVALID;
-    // the filter history and mixer uploads are ordered on the handle's stream: drain it first
-    DHIP(d, hipSetDevice(d->device));
-    DHIP(d, hipStreamSynchronize(d->stream));
-    if (d->own_stream == nullptr) d->own_stream = d->stream;
-    d->stream = stream ? (hipStream_t)stream : d->own_stream;
-    return RFA_OK;
-}
+int rfa_ddc_set_stream(rfa_ddc *d, void *stream) { return stage_set_stream(d, stream); }
 
 int rfa_ddc_get_ratio(const rfa_ddc *d, int32_t *interpolation, int32_t *decimation, int32_t *taps_per_output) {
     if (!d) return RFA_ERR_INVALID;
@@ -731,23 +661,20 @@ int rfa_resampler_design(int32_t output_rate, int32_t input_rate, int32_t max_de
 
 int rfa_ddc_destroy(rfa_ddc *d) {
     if (!d) return RFA_ERR_INVALID;
-    hipSetDevice(d->device);
-    if (d->stream) hipStreamSynchronize(d->stream);
+    stage_close_stream(d);
     for (void *p : {(void *)d->d_cos, (void *)d->d_taps, (void *)d->d_hist[0], (void *)d->d_hist[1], d->d_in,
                     (void *)d->d_out})
         if (p) hipFree(p);
-    hipStream_t own = d->own_stream ? d->own_stream : d->stream;
-    if (own) hipStreamDestroy(own);
     delete d;
     return RFA_OK;
 }
 
-const char *rfa_ddc_last_error(const rfa_ddc *d) { return d ? d->err.c_str() : "null handle"; }
+const char *rfa_ddc_last_error(const rfa_ddc *d) { return stage_last_error(d); }
 
 int rfa_ddc_set_sample_rate(rfa_ddc *d, int32_t sample_rate) {
     if (!d || sample_rate <= 0) return RFA_ERR_INVALID;
     if (sample_rate == d->sample_rate) return RFA_OK;
-    DHIP(d, hipSetDevice(d->device));
+    STAGE_HIP(d, hipSetDevice(d->device));
     const int32_t old = d->sample_rate;
     d->sample_rate = sample_rate;
     d->mixer_valid = false;                      // IQConverter.setSampleRate: cosineFrequency = -1
@@ -770,22 +697,22 @@ int rfa_ddc_set_frequencies(rfa_ddc *d, int64_t frequency, int64_t channel_frequ
     if (d->mixer_valid && mf == d->cos_freq) return RFA_OK;
     std::vector<float> c, s;
     mixer_table(d->fmt, d->sample_rate, mf, c, s);
-    if (c.size() * 8 > (size_t)kDynLds / 2) return dfail(d, RFA_ERR_UNSUPPORTED, "mixer table larger than half the LDS");
-    DHIP(d, hipSetDevice(d->device));
+    if (c.size() * 8 > (size_t)kDynLds / 2) return stage_fail(d, RFA_ERR_UNSUPPORTED, "mixer table larger than half the LDS");
+    STAGE_HIP(d, hipSetDevice(d->device));
     if (!c.empty()) {
         if (c.size() > d->d_cos_cap) {
-            DHIP(d, hipStreamSynchronize(d->stream));
+            STAGE_HIP(d, hipStreamSynchronize(d->stream));
             if (d->d_cos) (void)hipFree(d->d_cos);
             d->d_cos = nullptr;
             d->d_cos_cap = 0;
             if (hipMalloc(&d->d_cos, 2 * c.size() * sizeof(float)) != hipSuccess)
-                return dfail(d, RFA_ERR_NOMEM, "hipMalloc mixer table");
+                return stage_fail(d, RFA_ERR_NOMEM, "hipMalloc mixer table");
             d->d_cos_cap = c.size();
         }
-        DHIP(d, hipMemcpyAsync(d->d_cos, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
-        DHIP(d, hipMemcpyAsync(d->d_cos + d->d_cos_cap, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice,
+        STAGE_HIP(d, hipMemcpyAsync(d->d_cos, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
+        STAGE_HIP(d, hipMemcpyAsync(d->d_cos + d->d_cos_cap, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice,
                                d->stream));
-        DHIP(d, hipStreamSynchronize(d->stream));
+        STAGE_HIP(d, hipStreamSynchronize(d->stream));
     }
     d->cos_t = std::move(c);
     d->sin_t = std::move(s);
@@ -800,17 +727,17 @@ int rfa_ddc_process(rfa_ddc *d, const void *in, size_t n_samples, float *out_re,
     if (!d || !n_out) return RFA_ERR_INVALID;
     *n_out = 0;
     if (n_samples == 0) return RFA_OK;
-    const size_t sb = ddc_sample_bytes(d->fmt);
-    if (!in || (uintptr_t)in % std::min<size_t>(sb, 8) != 0) return dfail(d, RFA_ERR_INVALID, "input pointer null or misaligned");
-    if (n_samples > (size_t)1 << 40) return dfail(d, RFA_ERR_INVALID, "n_samples too large");
+    const size_t sb = stage_sample_bytes(d->fmt);
+    if (!in || (uintptr_t)in % std::min<size_t>(sb, 8) != 0) return stage_fail(d, RFA_ERR_INVALID, "input pointer null or misaligned");
+    if (n_samples > (size_t)1 << 40) return stage_fail(d, RFA_ERR_INVALID, "n_samples too large");
     const bool mixed = d->fmt != RFA_IN_F32_INTERLEAVED;
-    if (mixed && !d->mixer_valid) return dfail(d, RFA_ERR_STATE, "rfa_ddc_set_frequencies not called");
+    if (mixed && !d->mixer_valid) return stage_fail(d, RFA_ERR_STATE, "rfa_ddc_set_frequencies not called");
     if (mixed && d->cos_t.empty()) return RFA_OK;   // empty table: the reference mixes nothing
     const long long S = (long long)n_samples;
     const long long n = outputs_for(d, d->in_done + S) - d->n_done;
-    if ((size_t)n > out_capacity) return dfail(d, RFA_ERR_SIZE, "output capacity too small");
+    if ((size_t)n > out_capacity) return stage_fail(d, RFA_ERR_SIZE, "output capacity too small");
     if (n > 0 && (!out_re || !out_im)) return RFA_ERR_INVALID;
-    DHIP(d, hipSetDevice(d->device));
+    STAGE_HIP(d, hipSetDevice(d->device));
     DdcLaunch a{};
     a.raw = in;
     a.S = S;
@@ -830,17 +757,12 @@ int rfa_ddc_process(rfa_ddc *d, const void *in, size_t n_samples, float *out_re,
     a.n_out = n;
     plan_tiles(a);
     a.vec4 = mixed && ((uintptr_t)in % (4 * sb) == 0);
-    if ((n + a.P - 1) / a.P > (long long)INT32_MAX) return dfail(d, RFA_ERR_INVALID, "call too large for one grid");
+    if ((n + a.P - 1) / a.P > (long long)INT32_MAX) return stage_fail(d, RFA_ERR_INVALID, "call too large for one grid");
     a.out_re = out_re;
     a.out_im = out_im;
-    hipError_t e = hipSuccess;
-    switch (d->fmt) {
-    case RFA_IN_S8: e = dispatch<RFA_IN_S8>(a, d->stream); break;
-    case RFA_IN_U8: e = dispatch<RFA_IN_U8>(a, d->stream); break;
-    case RFA_IN_S16LE: e = dispatch<RFA_IN_S16LE>(a, d->stream); break;
-    default: e = dispatch<RFA_IN_F32_INTERLEAVED>(a, d->stream); break;
-    }
-    if (e != hipSuccess) return dfail(d, RFA_ERR_HIP, std::string("ddc launch: ") + hipGetErrorString(e));
+    const hipError_t e =
+        stage_dispatch_format(d->fmt, [&](auto f) { return launch_ddc<decltype(f)::value>(a, d->stream); });
+    if (e != hipSuccess) return stage_fail(d, RFA_ERR_HIP, std::string("ddc launch: ") + hipGetErrorString(e));
     if (a.T > 1) d->cur ^= 1;
     d->n_done += n;
     d->in_done += S;
@@ -854,48 +776,28 @@ int rfa_ddc_process_host(rfa_ddc *d, const void *in, size_t n_samples, float *ou
     if (!d || !n_out || (n_samples && !in)) return RFA_ERR_INVALID;
     *n_out = 0;
     if (n_samples == 0) return RFA_OK;
-    DHIP(d, hipSetDevice(d->device));
-    const size_t bytes = n_samples * ddc_sample_bytes(d->fmt);
+    STAGE_HIP(d, hipSetDevice(d->device));
+    const size_t bytes = n_samples * stage_sample_bytes(d->fmt);
     const size_t most = (size_t)(outputs_for(d, d->in_done + (long long)n_samples) - d->n_done) + 1;
-    if (bytes > d->d_in_cap) {
-        if (d->d_in) hipFree(d->d_in);
-        d->d_in = nullptr;
-        d->d_in_cap = 0;
-        if (hipMalloc(&d->d_in, bytes) != hipSuccess) return dfail(d, RFA_ERR_NOMEM, "hipMalloc input staging");
-        d->d_in_cap = bytes;
-    }
-    if (2 * most > d->d_out_cap) {
-        if (d->d_out) hipFree(d->d_out);
-        d->d_out = nullptr;
-        d->d_out_cap = 0;
-        if (hipMalloc(&d->d_out, 2 * most * sizeof(float)) != hipSuccess) return dfail(d, RFA_ERR_NOMEM, "hipMalloc output staging");
-        d->d_out_cap = 2 * most;
-    }
-    DHIP(d, hipMemcpyAsync(d->d_in, in, bytes, hipMemcpyHostToDevice, d->stream));
+    int rc = stage_grow(d, d->d_in, d->d_in_cap, bytes, "input staging");
+    if (rc == RFA_OK) rc = stage_grow(d, d->d_out, d->d_out_cap, 2 * most, "output staging");
+    if (rc != RFA_OK) return rc;
+    STAGE_HIP(d, hipMemcpyAsync(d->d_in, in, bytes, hipMemcpyHostToDevice, d->stream));
     size_t n = 0;
-    const int rc = rfa_ddc_process(d, d->d_in, n_samples, d->d_out, d->d_out + most, out_capacity, &n);
+    rc = rfa_ddc_process(d, d->d_in, n_samples, d->d_out, d->d_out + most, out_capacity, &n);
     if (rc != RFA_OK) return rc;
     if (n) {
-        DHIP(d, hipMemcpyAsync(out_re, d->d_out, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-        DHIP(d, hipMemcpyAsync(out_im, d->d_out + most, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+        STAGE_HIP(d, hipMemcpyAsync(out_re, d->d_out, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+        STAGE_HIP(d, hipMemcpyAsync(out_im, d->d_out + most, n * sizeof(float), hipMemcpyDeviceToHost, d->stream));
     }
-    DHIP(d, hipStreamSynchronize(d->stream));
+    STAGE_HIP(d, hipStreamSynchronize(d->stream));
     *n_out = n;
     return RFA_OK;
 }
 
-int rfa_ddc_synchronize(rfa_ddc *d) {
-    if (!d) return RFA_ERR_INVALID;
-    DHIP(d, hipSetDevice(d->device));
-    DHIP(d, hipStreamSynchronize(d->stream));
-    return RFA_OK;
-}
+int rfa_ddc_synchronize(rfa_ddc *d) { return stage_synchronize(d); }
 
-int rfa_ddc_get_stream(const rfa_ddc *d, void **stream) {
-    if (!d || !stream) return RFA_ERR_INVALID;
-    *stream = (void *)d->stream;
-    return RFA_OK;
-}
+int rfa_ddc_get_stream(const rfa_ddc *d, void **stream) { return stage_get_stream(d, stream); }
 
 int rfa_ddc_get_taps(const rfa_ddc *d, float *taps, size_t capacity, int32_t *num_taps, int32_t *decimation) {
     if (!d) return RFA_ERR_INVALID;
@@ -956,17 +858,6 @@ struct rfa_ddc_bank {
 
 namespace {
 
-int bfail(rfa_ddc_bank *b, int code, const std::string &msg) {
-    if (b) b->err = msg;
-    return code;
-}
-
-#define BHIP(b, expr)                                                                  \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess) return bfail((b), RFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 // status of a call made on the shared handle, with its message
 int bcore(rfa_ddc_bank *b, int rc) {
     if (rc != RFA_OK) b->err = b->core->err;
@@ -985,11 +876,11 @@ int bank_reset_history(rfa_ddc_bank *b) {
             if (h) (void)hipFree(h), h = nullptr;
         b->hist_cap = 0;
         for (float *&h : b->d_hist)
-            if (hipMalloc(&h, need * sizeof(float)) != hipSuccess) return bfail(b, RFA_ERR_NOMEM, "hipMalloc bank history");
+            if (hipMalloc(&h, need * sizeof(float)) != hipSuccess) return stage_fail(b, RFA_ERR_NOMEM, "hipMalloc bank history");
         b->hist_cap = need;
     }
-    BHIP(b, hipMemsetAsync(b->d_hist[0], 0, need * sizeof(float), b->core->stream));
-    BHIP(b, hipStreamSynchronize(b->core->stream));
+    STAGE_HIP(b, hipMemsetAsync(b->d_hist[0], 0, need * sizeof(float), b->core->stream));
+    STAGE_HIP(b, hipStreamSynchronize(b->core->stream));
     return RFA_OK;
 }
 
@@ -999,7 +890,7 @@ extern "C" {
 
 int rfa_ddc_mix_info(int input_format, int32_t sample_rate, int64_t frequency, int64_t channel_frequency,
                      int32_t *mix_frequency, int32_t *table_length) {
-    if (ddc_sample_bytes(input_format) == 0 || sample_rate <= 0) return RFA_ERR_INVALID;
+    if (stage_sample_bytes(input_format) == 0 || sample_rate <= 0) return RFA_ERR_INVALID;
     if (input_format == RFA_IN_F32_INTERLEAVED) return RFA_ERR_UNSUPPORTED;   // no mixer: samples arrive mixed
     const int32_t mf = fold_mix(frequency, channel_frequency, sample_rate);
     if (mix_frequency) *mix_frequency = mf;
@@ -1032,7 +923,7 @@ int rfa_ddc_bank_create(int device, int input_format, int32_t sample_rate, int32
                         int32_t n_channels, rfa_ddc_bank **out) {
     if (!out) return RFA_ERR_INVALID;
     *out = nullptr;
-    if (ddc_sample_bytes(input_format) == 0 || sample_rate <= 0 || output_sample_rate <= 0) return RFA_ERR_INVALID;
+    if (stage_sample_bytes(input_format) == 0 || sample_rate <= 0 || output_sample_rate <= 0) return RFA_ERR_INVALID;
     if (resampler != 0 && resampler != 1) return RFA_ERR_INVALID;
     if (n_channels < 1 || n_channels > kBankMaxChannels) return RFA_ERR_INVALID;
     if (input_format == RFA_IN_F32_INTERLEAVED) return RFA_ERR_UNSUPPORTED;   // every slot would be the same channel
@@ -1055,8 +946,7 @@ int rfa_ddc_bank_create(int device, int input_format, int32_t sample_rate, int32
 int rfa_ddc_bank_destroy(rfa_ddc_bank *b) {
     if (!b) return RFA_ERR_INVALID;
     if (b->core) {
-        hipSetDevice(b->core->device);
-        if (b->core->stream) hipStreamSynchronize(b->core->stream);
+        (void)stage_synchronize(b->core);
         for (void *p : {(void *)b->d_tab, (void *)b->d_slots, (void *)b->d_hist[0], (void *)b->d_hist[1], b->d_in,
                         (void *)b->d_out})
             if (p) hipFree(p);
@@ -1066,7 +956,7 @@ int rfa_ddc_bank_destroy(rfa_ddc_bank *b) {
     return RFA_OK;
 }
 
-const char *rfa_ddc_bank_last_error(const rfa_ddc_bank *b) { return b ? b->err.c_str() : "null handle"; }
+const char *rfa_ddc_bank_last_error(const rfa_ddc_bank *b) { return stage_last_error(b); }
 
 int rfa_ddc_bank_set_stream(rfa_ddc_bank *b, void *stream) {
     if (!b) return RFA_ERR_INVALID;
@@ -1124,9 +1014,9 @@ int rfa_ddc_bank_set_frequencies(rfa_ddc_bank *b, int64_t frequency, const int64
         if (old.valid && mf == old.cos_freq) continue;           // keeps its table and cosine index
         mixer_table(d->fmt, d->sample_rate, mf, s.cos_t, s.sin_t);
         if (s.cos_t.empty())
-            return bfail(b, RFA_ERR_UNSUPPORTED, "slot " + std::to_string(k) + ": empty mixer table");
+            return stage_fail(b, RFA_ERR_UNSUPPORTED, "slot " + std::to_string(k) + ": empty mixer table");
         if (s.cos_t.size() * 8 > (size_t)kDynLds / 2)
-            return bfail(b, RFA_ERR_UNSUPPORTED, "slot " + std::to_string(k) + ": mixer table larger than half the LDS");
+            return stage_fail(b, RFA_ERR_UNSUPPORTED, "slot " + std::to_string(k) + ": mixer table larger than half the LDS");
         s.cos_freq = mf;
         s.valid = changed = true;
     }
@@ -1147,19 +1037,19 @@ int rfa_ddc_bank_set_frequencies(rfa_ddc_bank *b, int64_t frequency, const int64
         pool.insert(pool.end(), s.sin_t.begin(), s.sin_t.end());
         l_max = std::max(l_max, L);
     }
-    BHIP(b, hipSetDevice(d->device));
+    STAGE_HIP(b, hipSetDevice(d->device));
     if (pool.size() > b->tab_cap) {
-        BHIP(b, hipStreamSynchronize(d->stream));
+        STAGE_HIP(b, hipStreamSynchronize(d->stream));
         float *p = nullptr;
-        if (hipMalloc(&p, pool.size() * sizeof(float)) != hipSuccess) return bfail(b, RFA_ERR_NOMEM, "hipMalloc mixer tables");
+        if (hipMalloc(&p, pool.size() * sizeof(float)) != hipSuccess) return stage_fail(b, RFA_ERR_NOMEM, "hipMalloc mixer tables");
         if (b->d_tab) (void)hipFree(b->d_tab);
         b->d_tab = p;
         b->tab_cap = pool.size();
         for (auto &s : b->slots) s.valid = false;                // the old pool went with its tables
     }
-    BHIP(b, hipMemcpyAsync(b->d_tab, pool.data(), pool.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
-    BHIP(b, hipMemcpyAsync(b->d_slots, desc.data(), K * sizeof(BankSlot), hipMemcpyHostToDevice, d->stream));
-    BHIP(b, hipStreamSynchronize(d->stream));
+    STAGE_HIP(b, hipMemcpyAsync(b->d_tab, pool.data(), pool.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    STAGE_HIP(b, hipMemcpyAsync(b->d_slots, desc.data(), K * sizeof(BankSlot), hipMemcpyHostToDevice, d->stream));
+    STAGE_HIP(b, hipStreamSynchronize(d->stream));
     b->slots = std::move(ns);
     b->l_max = (int)l_max;
     return RFA_OK;
@@ -1189,18 +1079,18 @@ int rfa_ddc_bank_process(rfa_ddc_bank *b, const void *in, size_t n_samples, floa
     *n_out = 0;
     if (n_samples == 0) return RFA_OK;
     rfa_ddc *d = b->core;
-    const size_t sb = ddc_sample_bytes(d->fmt);
-    if (!in || (uintptr_t)in % std::min<size_t>(sb, 8) != 0) return bfail(b, RFA_ERR_INVALID, "input pointer null or misaligned");
-    if (n_samples > (size_t)1 << 40) return bfail(b, RFA_ERR_INVALID, "n_samples too large");
+    const size_t sb = stage_sample_bytes(d->fmt);
+    if (!in || (uintptr_t)in % std::min<size_t>(sb, 8) != 0) return stage_fail(b, RFA_ERR_INVALID, "input pointer null or misaligned");
+    if (n_samples > (size_t)1 << 40) return stage_fail(b, RFA_ERR_INVALID, "n_samples too large");
     const int K = (int)b->slots.size();
     for (const auto &s : b->slots)
-        if (!s.valid) return bfail(b, RFA_ERR_STATE, "rfa_ddc_bank_set_frequencies not called");
-    if (b->hist_cap < (size_t)K * 2 * (size_t)(d->T - 1)) return bfail(b, RFA_ERR_STATE, "no delay lines (allocation failed earlier)");
+        if (!s.valid) return stage_fail(b, RFA_ERR_STATE, "rfa_ddc_bank_set_frequencies not called");
+    if (b->hist_cap < (size_t)K * 2 * (size_t)(d->T - 1)) return stage_fail(b, RFA_ERR_STATE, "no delay lines (allocation failed earlier)");
     const long long S = (long long)n_samples;
     const long long n = outputs_for(d, d->in_done + S) - d->n_done;
-    if ((size_t)n > channel_stride) return bfail(b, RFA_ERR_SIZE, "channel_stride smaller than the output count");
+    if ((size_t)n > channel_stride) return stage_fail(b, RFA_ERR_SIZE, "channel_stride smaller than the output count");
     if (n > 0 && (!out_re || !out_im)) return RFA_ERR_INVALID;
-    BHIP(b, hipSetDevice(d->device));
+    STAGE_HIP(b, hipSetDevice(d->device));
     DdcLaunch a{};
     a.raw = in;
     a.S = S;
@@ -1225,17 +1115,16 @@ int rfa_ddc_bank_process(rfa_ddc_bank *b, const void *in, size_t n_samples, floa
     bl.hist_pitch = 2LL * (d->T - 1);
     bl.out_pitch = (long long)channel_stride;
     if ((n + a.P - 1) / a.P * std::min(K, kBankLaunchSlots) > (long long)INT32_MAX)
-        return bfail(b, RFA_ERR_INVALID, "call too large for one grid");
+        return stage_fail(b, RFA_ERR_INVALID, "call too large for one grid");
     for (int k0 = 0; k0 < K; k0 += kBankLaunchSlots) {
         bl.slot0 = k0;
         bl.nslots = std::min(kBankLaunchSlots, K - k0);
-        hipError_t e = hipSuccess;
-        switch (d->fmt) {
-        case RFA_IN_S8: e = launch_ddc_bank<RFA_IN_S8>(a, bl, d->stream); break;
-        case RFA_IN_U8: e = launch_ddc_bank<RFA_IN_U8>(a, bl, d->stream); break;
-        default: e = launch_ddc_bank<RFA_IN_S16LE>(a, bl, d->stream); break;
-        }
-        if (e != hipSuccess) return bfail(b, RFA_ERR_HIP, std::string("ddc bank launch: ") + hipGetErrorString(e));
+        const hipError_t e = stage_dispatch_format(d->fmt, [&](auto f) {
+            constexpr int FMT = decltype(f)::value;
+            if constexpr (FMT == RFA_IN_F32_INTERLEAVED) return hipErrorInvalidValue;   // refused at creation
+            else return launch_ddc_bank<FMT>(a, bl, d->stream);
+        });
+        if (e != hipSuccess) return stage_fail(b, RFA_ERR_HIP, std::string("ddc bank launch: ") + hipGetErrorString(e));
     }
     if (a.T > 1) d->cur ^= 1;
     d->n_done += n;
@@ -1250,38 +1139,28 @@ int rfa_ddc_bank_process_host(rfa_ddc_bank *b, const void *in, size_t n_samples,
     *n_out = 0;
     if (n_samples == 0) return RFA_OK;
     rfa_ddc *d = b->core;
-    if (n_samples > (size_t)1 << 40) return bfail(b, RFA_ERR_INVALID, "n_samples too large");
-    BHIP(b, hipSetDevice(d->device));
+    if (n_samples > (size_t)1 << 40) return stage_fail(b, RFA_ERR_INVALID, "n_samples too large");
+    STAGE_HIP(b, hipSetDevice(d->device));
     const size_t K = b->slots.size();
-    const size_t bytes = n_samples * ddc_sample_bytes(d->fmt);
+    const size_t bytes = n_samples * stage_sample_bytes(d->fmt);
     const size_t most = (size_t)(outputs_for(d, d->in_done + (long long)n_samples) - d->n_done);
-    if (most > channel_stride) return bfail(b, RFA_ERR_SIZE, "channel_stride smaller than the output count");
-    if (bytes > b->d_in_cap) {
-        if (b->d_in) hipFree(b->d_in);
-        b->d_in = nullptr;
-        b->d_in_cap = 0;
-        if (hipMalloc(&b->d_in, bytes) != hipSuccess) return bfail(b, RFA_ERR_NOMEM, "hipMalloc input staging");
-        b->d_in_cap = bytes;
-    }
+    if (most > channel_stride) return stage_fail(b, RFA_ERR_SIZE, "channel_stride smaller than the output count");
     const size_t pitch = most + 1;
-    if (2 * K * pitch > b->d_out_cap) {
-        if (b->d_out) hipFree(b->d_out);
-        b->d_out = nullptr;
-        b->d_out_cap = 0;
-        if (hipMalloc(&b->d_out, 2 * K * pitch * sizeof(float)) != hipSuccess) return bfail(b, RFA_ERR_NOMEM, "hipMalloc output staging");
-        b->d_out_cap = 2 * K * pitch;
-    }
-    BHIP(b, hipMemcpyAsync(b->d_in, in, bytes, hipMemcpyHostToDevice, d->stream));
+    // the staging buffers are the bank's; stream and error text come from the shared handle
+    int rc = stage_grow(d, b->d_in, b->d_in_cap, bytes, "input staging");
+    if (rc == RFA_OK) rc = stage_grow(d, b->d_out, b->d_out_cap, 2 * K * pitch, "output staging");
+    if (rc != RFA_OK) return bcore(b, rc);
+    STAGE_HIP(b, hipMemcpyAsync(b->d_in, in, bytes, hipMemcpyHostToDevice, d->stream));
     size_t n = 0;
-    const int rc = rfa_ddc_bank_process(b, b->d_in, n_samples, b->d_out, b->d_out + K * pitch, pitch, &n);
+    rc = rfa_ddc_bank_process(b, b->d_in, n_samples, b->d_out, b->d_out + K * pitch, pitch, &n);
     if (rc != RFA_OK) return rc;
     if (n) {
-        BHIP(b, hipMemcpy2DAsync(out_re, channel_stride * sizeof(float), b->d_out, pitch * sizeof(float),
+        STAGE_HIP(b, hipMemcpy2DAsync(out_re, channel_stride * sizeof(float), b->d_out, pitch * sizeof(float),
                                  n * sizeof(float), K, hipMemcpyDeviceToHost, d->stream));
-        BHIP(b, hipMemcpy2DAsync(out_im, channel_stride * sizeof(float), b->d_out + K * pitch, pitch * sizeof(float),
+        STAGE_HIP(b, hipMemcpy2DAsync(out_im, channel_stride * sizeof(float), b->d_out + K * pitch, pitch * sizeof(float),
                                  n * sizeof(float), K, hipMemcpyDeviceToHost, d->stream));
     }
-    BHIP(b, hipStreamSynchronize(d->stream));
+    STAGE_HIP(b, hipStreamSynchronize(d->stream));
     *n_out = n;
     return RFA_OK;
 }

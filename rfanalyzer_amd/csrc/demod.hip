@@ -41,6 +41,8 @@
 
 #pragma clang fp contract(off)
 
+#include "stage_common.h"
+
 namespace {
 
 constexpr int kTile = 256;               // outputs per workgroup
@@ -349,10 +351,7 @@ struct DemodSlot {
 
 }  // namespace
 
-struct rfa_demod : DemodSlot {
-    int device = 0;
-    hipStream_t stream = nullptr, own_stream = nullptr;
-    std::string err;
+struct rfa_demod : DemodSlot, StageCore {
     // device
     float *d_state[2] = {nullptr, nullptr};
     int cur = 0;
@@ -366,18 +365,6 @@ struct rfa_demod : DemodSlot {
 };
 
 namespace {
-
-template <class H>   // rfa_demod or rfa_demod_bank
-int mfail(H *d, int code, const std::string &msg) {
-    if (d) d->err = msg;
-    return code;
-}
-
-#define MHIP(d, expr)                                                                  \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess) return mfail((d), RFA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 // Demodulator.kt:217: userFilter == null || cutOffFrequency.toInt() != channelWidth
 bool uf_stale(const DemodSlot *d) { return !d->uf_valid || jtoint((double)d->uf_cutoff) != d->width; }
@@ -429,8 +416,8 @@ void make_plan(const DemodSlot *d, long long n, long long packet, Plan &p) {
 }
 
 int upload_taps(rfa_demod *d, int at, const std::vector<float> &t) {
-    MHIP(d, hipMemcpyAsync(d->d_taps + at, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
-    MHIP(d, hipStreamSynchronize(d->stream));
+    STAGE_HIP(d, hipMemcpyAsync(d->d_taps + at, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice, d->stream));
+    STAGE_HIP(d, hipStreamSynchronize(d->stream));
     return RFA_OK;
 }
 
@@ -501,8 +488,8 @@ int rebuild_user_filter(rfa_demod *d) {
     Design g;
     const char *why = "";
     const int st = design_user_filter(d, g, why);
-    if (st != RFA_OK) return mfail(d, st, why);
-    MHIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_UF_RE, 0, 2 * kMaxUserTaps * sizeof(float), d->stream));
+    if (st != RFA_OK) return stage_fail(d, st, why);
+    STAGE_HIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_UF_RE, 0, 2 * kMaxUserTaps * sizeof(float), d->stream));
     const int rc = upload_taps(d, TP_UF, g.uf_taps);
     if (rc != RFA_OK) return rc;
     commit_user_filter(d, g);
@@ -513,8 +500,8 @@ int rebuild_band_pass(rfa_demod *d) {
     Design g;
     const char *why = "";
     const int st = design_band_pass_filter(d, g, why);
-    if (st != RFA_OK) return mfail(d, st, why);
-    MHIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_BP_RE, 0, 2 * kMaxBandTaps * sizeof(float), d->stream));
+    if (st != RFA_OK) return stage_fail(d, st, why);
+    STAGE_HIP(d, hipMemsetAsync(d->d_state[d->cur] + ST_BP_RE, 0, 2 * kMaxBandTaps * sizeof(float), d->stream));
     int rc = upload_taps(d, TP_BPR, g.bp_re);
     if (rc == RFA_OK) rc = upload_taps(d, TP_BPI, g.bp_im);
     if (rc != RFA_OK) return rc;
@@ -626,21 +613,8 @@ int slot_get_taps(const DemodSlot *d, int which, float *re, float *im, size_t ca
 // A freshly created Demodulator + AudioSink: no user or band-pass filter, zero
 // carry-over and lastMax, audio filters with empty delay lines.
 int fresh_state(rfa_demod *d) {
-    MHIP(d, hipMemsetAsync(d->d_state[d->cur], 0, ST_SIZE * sizeof(float), d->stream));
+    STAGE_HIP(d, hipMemsetAsync(d->d_state[d->cur], 0, ST_SIZE * sizeof(float), d->stream));
     forget_filters(d);
-    return RFA_OK;
-}
-
-template <class H>
-int grow(H *d, float *&p, size_t &cap, size_t want, const char *what) {
-    if (want <= cap) return RFA_OK;
-    MHIP(d, hipStreamSynchronize(d->stream));
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    want = std::max(want, (size_t)4096);
-    if (hipMalloc(&p, want * sizeof(float)) != hipSuccess) return mfail(d, RFA_ERR_NOMEM, std::string("hipMalloc ") + what);
-    cap = want;
     return RFA_OK;
 }
 
@@ -678,20 +652,16 @@ int rfa_demod_create(int device, int mode, rfa_demod **out) {
     if (!out) return RFA_ERR_INVALID;
     *out = nullptr;
     if (!mode_ok(mode)) return RFA_ERR_INVALID;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
-    if (device < 0 || device >= count) return RFA_ERR_INVALID;
+    int rc = stage_check_device(device);
+    if (rc != RFA_OK) return rc;
     rfa_demod *d = new (std::nothrow) rfa_demod();
     if (!d) return RFA_ERR_NOMEM;
     d->device = device;
     d->mode = mode;
     d->width = kModes[mode].def_w;
-    int rc = RFA_OK;
     std::vector<float> t1, t2;
     if (!design_audio_filters(t1, t2)) rc = RFA_ERR_INVALID;
-    if (rc == RFA_OK && (hipSetDevice(device) != hipSuccess ||
-                         hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess))
-        rc = RFA_ERR_HIP;
+    if (rc == RFA_OK) rc = stage_open(d, device);
     if (rc == RFA_OK) {
         if (hipMalloc(&d->d_state[0], ST_SIZE * sizeof(float)) != hipSuccess ||
             hipMalloc(&d->d_state[1], ST_SIZE * sizeof(float)) != hipSuccess ||
@@ -716,21 +686,18 @@ int rfa_demod_create(int device, int mode, rfa_demod **out) {
 
 int rfa_demod_destroy(rfa_demod *d) {
     if (!d) return RFA_ERR_INVALID;
-    (void)hipSetDevice(d->device);
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    stage_close_stream(d);
     for (float *p : {d->d_state[0], d->d_state[1], d->d_taps, d->d_pre, d->d_pk, d->d_in, d->d_out})
         if (p) (void)hipFree(p);
-    hipStream_t own = d->own_stream ? d->own_stream : d->stream;
-    if (own) (void)hipStreamDestroy(own);
     delete d;
     return RFA_OK;
 }
 
-const char *rfa_demod_last_error(const rfa_demod *d) { return d ? d->err.c_str() : "null handle"; }
+const char *rfa_demod_last_error(const rfa_demod *d) { return stage_last_error(d); }
 
 int rfa_demod_set_mode(rfa_demod *d, int mode) {
     if (!d) return RFA_ERR_INVALID;
-    if (!mode_ok(mode)) return mfail(d, RFA_ERR_INVALID, "no such demodulation mode");
+    if (!mode_ok(mode)) return stage_fail(d, RFA_ERR_INVALID, "no such demodulation mode");
     slot_set_mode(d, mode);
     return RFA_OK;
 }
@@ -782,17 +749,17 @@ int rfa_demod_process(rfa_demod *d, const float *re, const float *im, size_t n_s
     *n_audio = 0;
     if (d->mode == RFA_DEMOD_OFF) return RFA_OK;          // Demodulator.kt:174: no output, nothing moves
     if (n_samples > (size_t)1 << 36 || packet_samples > (size_t)1 << 36)
-        return mfail(d, RFA_ERR_INVALID, "n_samples too large");
-    if (n_samples && (!re || !im)) return mfail(d, RFA_ERR_INVALID, "null input");
+        return stage_fail(d, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return stage_fail(d, RFA_ERR_INVALID, "null input");
     Plan p;
     make_plan(d, (long long)n_samples, (long long)packet_samples, p);
-    if ((size_t)p.n_audio > capacity) return mfail(d, RFA_ERR_SIZE, "audio capacity too small");
-    if (p.n_audio > 0 && !audio) return mfail(d, RFA_ERR_INVALID, "null output");
+    if ((size_t)p.n_audio > capacity) return stage_fail(d, RFA_ERR_SIZE, "audio capacity too small");
+    if (p.n_audio > 0 && !audio) return stage_fail(d, RFA_ERR_INVALID, "null output");
     if (p.K > (long long)INT32_MAX || (p.npre + kTile - 1) / kTile > (long long)INT32_MAX)
-        return mfail(d, RFA_ERR_INVALID, "call too large for one grid");
-    MHIP(d, hipSetDevice(d->device));
-    int rc = grow(d, d->d_pre, d->pre_cap, (size_t)p.npre, "scratch");
-    if (rc == RFA_OK) rc = grow(d, d->d_pk, d->pk_cap, 3 * (size_t)p.K, "packet scratch");
+        return stage_fail(d, RFA_ERR_INVALID, "call too large for one grid");
+    STAGE_HIP(d, hipSetDevice(d->device));
+    int rc = stage_grow(d, d->d_pre, d->pre_cap, (size_t)p.npre, "scratch");
+    if (rc == RFA_OK) rc = stage_grow(d, d->d_pk, d->pk_cap, 3 * (size_t)p.K, "packet scratch");
     if (rc == RFA_OK && p.uf_fresh) rc = rebuild_user_filter(d);
     if (rc == RFA_OK && p.bp_fresh) rc = rebuild_band_pass(d);
     if (rc != RFA_OK) return rc;
@@ -813,18 +780,18 @@ int rfa_demod_process(rfa_demod *d, const float *re, const float *im, size_t n_s
     if (p.npre > 0) {
         hipLaunchKernelGGL(demod_stage1_kernel, dim3((unsigned)((p.npre + kTile - 1) / kTile)), dim3(kTile), 0,
                            d->stream, a);
-        MHIP(d, hipGetLastError());
+        STAGE_HIP(d, hipGetLastError());
     }
     if (a.agc) {
         hipLaunchKernelGGL(demod_packet_kernel, dim3((unsigned)p.K), dim3(64), 0, d->stream, a);
-        MHIP(d, hipGetLastError());
+        STAGE_HIP(d, hipGetLastError());
     }
     hipLaunchKernelGGL(demod_state_kernel, dim3(1), dim3(kTile), 0, d->stream, a);
-    MHIP(d, hipGetLastError());
+    STAGE_HIP(d, hipGetLastError());
     if (p.n_audio > 0) {
         hipLaunchKernelGGL(demod_audio_kernel, dim3((unsigned)((p.n_audio + kTile - 1) / kTile)), dim3(kTile), 0,
                            d->stream, a);
-        MHIP(d, hipGetLastError());
+        STAGE_HIP(d, hipGetLastError());
     }
     d->cur ^= 1;
     advance(d, p, (long long)n_samples);
@@ -837,24 +804,24 @@ int rfa_demod_process_host(rfa_demod *d, const float *re, const float *im, size_
     if (!d || !n_audio) return RFA_ERR_INVALID;
     *n_audio = 0;
     if (d->mode == RFA_DEMOD_OFF) return RFA_OK;
-    if (n_samples > (size_t)1 << 36) return mfail(d, RFA_ERR_INVALID, "n_samples too large");
-    if (n_samples && (!re || !im)) return mfail(d, RFA_ERR_INVALID, "null input");
-    MHIP(d, hipSetDevice(d->device));
+    if (n_samples > (size_t)1 << 36) return stage_fail(d, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return stage_fail(d, RFA_ERR_INVALID, "null input");
+    STAGE_HIP(d, hipSetDevice(d->device));
     Plan p;
     make_plan(d, (long long)n_samples, (long long)packet_samples, p);
-    if ((size_t)p.n_audio > capacity) return mfail(d, RFA_ERR_SIZE, "audio capacity too small");
-    int rc = grow(d, d->d_in, d->d_in_cap, 2 * n_samples, "input staging");
-    if (rc == RFA_OK) rc = grow(d, d->d_out, d->d_out_cap, (size_t)p.n_audio, "output staging");
+    if ((size_t)p.n_audio > capacity) return stage_fail(d, RFA_ERR_SIZE, "audio capacity too small");
+    int rc = stage_grow(d, d->d_in, d->d_in_cap, 2 * n_samples, "input staging");
+    if (rc == RFA_OK) rc = stage_grow(d, d->d_out, d->d_out_cap, (size_t)p.n_audio, "output staging");
     if (rc != RFA_OK) return rc;
     if (n_samples) {
-        MHIP(d, hipMemcpyAsync(d->d_in, re, n_samples * sizeof(float), hipMemcpyHostToDevice, d->stream));
-        MHIP(d, hipMemcpyAsync(d->d_in + n_samples, im, n_samples * sizeof(float), hipMemcpyHostToDevice, d->stream));
+        STAGE_HIP(d, hipMemcpyAsync(d->d_in, re, n_samples * sizeof(float), hipMemcpyHostToDevice, d->stream));
+        STAGE_HIP(d, hipMemcpyAsync(d->d_in + n_samples, im, n_samples * sizeof(float), hipMemcpyHostToDevice, d->stream));
     }
     size_t got = 0;
     rc = rfa_demod_process(d, d->d_in, d->d_in + n_samples, n_samples, packet_samples, d->d_out, d->d_out_cap, &got);
     if (rc != RFA_OK) return rc;
-    if (got) MHIP(d, hipMemcpyAsync(audio, d->d_out, got * sizeof(float), hipMemcpyDeviceToHost, d->stream));
-    MHIP(d, hipStreamSynchronize(d->stream));
+    if (got) STAGE_HIP(d, hipMemcpyAsync(audio, d->d_out, got * sizeof(float), hipMemcpyDeviceToHost, d->stream));
+    STAGE_HIP(d, hipStreamSynchronize(d->stream));
     *n_audio = got;
     return RFA_OK;
 }
@@ -867,10 +834,10 @@ int rfa_demod_get_taps(const rfa_demod *d, int which, float *re, float *im, size
 
 int rfa_demod_get_state(rfa_demod *d, float *last_max, float *carry_re, float *carry_im) {
     if (!d) return RFA_ERR_INVALID;
-    MHIP(d, hipSetDevice(d->device));
+    STAGE_HIP(d, hipSetDevice(d->device));
     float s[3] = {0.0f, 0.0f, 0.0f};
-    MHIP(d, hipMemcpyAsync(s, d->d_state[d->cur] + ST_CARRY, sizeof s, hipMemcpyDeviceToHost, d->stream));
-    MHIP(d, hipStreamSynchronize(d->stream));
+    STAGE_HIP(d, hipMemcpyAsync(s, d->d_state[d->cur] + ST_CARRY, sizeof s, hipMemcpyDeviceToHost, d->stream));
+    STAGE_HIP(d, hipStreamSynchronize(d->stream));
     if (carry_re) *carry_re = s[0];
     if (carry_im) *carry_im = s[1];
     if (last_max) *last_max = s[2];
@@ -879,32 +846,15 @@ int rfa_demod_get_state(rfa_demod *d, float *last_max, float *carry_re, float *c
 
 int rfa_demod_reset(rfa_demod *d) {
     if (!d) return RFA_ERR_INVALID;
-    MHIP(d, hipSetDevice(d->device));
+    STAGE_HIP(d, hipSetDevice(d->device));
     return fresh_state(d);
 }
 
-int rfa_demod_set_stream(rfa_demod *d, void *stream) {
-    if (!d) return RFA_ERR_INVALID;
-    // the carried state is ordered on the handle's stream: drain it first
-    MHIP(d, hipSetDevice(d->device));
-    MHIP(d, hipStreamSynchronize(d->stream));
-    if (d->own_stream == nullptr) d->own_stream = d->stream;
-    d->stream = stream ? (hipStream_t)stream : d->own_stream;
-    return RFA_OK;
-}
+int rfa_demod_set_stream(rfa_demod *d, void *stream) { return stage_set_stream(d, stream); }
 
-int rfa_demod_get_stream(const rfa_demod *d, void **stream) {
-    if (!d || !stream) return RFA_ERR_INVALID;
-    *stream = (void *)d->stream;
-    return RFA_OK;
-}
+int rfa_demod_get_stream(const rfa_demod *d, void **stream) { return stage_get_stream(d, stream); }
 
-int rfa_demod_synchronize(rfa_demod *d) {
-    if (!d) return RFA_ERR_INVALID;
-    MHIP(d, hipSetDevice(d->device));
-    MHIP(d, hipStreamSynchronize(d->stream));
-    return RFA_OK;
-}
+int rfa_demod_synchronize(rfa_demod *d) { return stage_synchronize(d); }
 
 }  // extern "C"
 
@@ -922,11 +872,8 @@ int rfa_demod_synchronize(rfa_demod *d) {
 
 constexpr int kRecRing = 8;
 
-struct rfa_demod_bank {
-    int device = 0;
+struct rfa_demod_bank : StageCore {
     int K = 0;
-    hipStream_t stream = nullptr, own_stream = nullptr;
-    std::string err;
     std::vector<DemodSlot> slots;
     std::vector<int> cur;              // which copy of slot k's state is current
     std::vector<Plan> plans;           // per call, kept to allocate nothing in steady state
@@ -975,25 +922,25 @@ int bank_rebuild(rfa_demod_bank *b) {
         int st = RFA_OK;
         if (p.uf_fresh) st = design_user_filter(s, g, why);
         if (st == RFA_OK && p.bp_fresh) st = design_band_pass_filter(s, g, why);
-        if (st != RFA_OK) return mfail(b, st, "slot " + std::to_string(k) + ": " + why);
+        if (st != RFA_OK) return stage_fail(b, st, "slot " + std::to_string(k) + ": " + why);
     }
     if (todo.empty()) return RFA_OK;
     for (auto &[k, g] : todo) {
         float *st = bank_state(b, k, b->cur[k]), *tp = b->d_taps + (size_t)k * TP_SIZE;
         if (g.uf) {
-            MHIP(b, hipMemsetAsync(st + ST_UF_RE, 0, 2 * kMaxUserTaps * sizeof(float), b->stream));
-            MHIP(b, hipMemcpyAsync(tp + TP_UF, g.uf_taps.data(), g.uf_taps.size() * sizeof(float),
+            STAGE_HIP(b, hipMemsetAsync(st + ST_UF_RE, 0, 2 * kMaxUserTaps * sizeof(float), b->stream));
+            STAGE_HIP(b, hipMemcpyAsync(tp + TP_UF, g.uf_taps.data(), g.uf_taps.size() * sizeof(float),
                                    hipMemcpyHostToDevice, b->stream));
         }
         if (g.bp) {
-            MHIP(b, hipMemsetAsync(st + ST_BP_RE, 0, 2 * kMaxBandTaps * sizeof(float), b->stream));
-            MHIP(b, hipMemcpyAsync(tp + TP_BPR, g.bp_re.data(), g.bp_re.size() * sizeof(float), hipMemcpyHostToDevice,
+            STAGE_HIP(b, hipMemsetAsync(st + ST_BP_RE, 0, 2 * kMaxBandTaps * sizeof(float), b->stream));
+            STAGE_HIP(b, hipMemcpyAsync(tp + TP_BPR, g.bp_re.data(), g.bp_re.size() * sizeof(float), hipMemcpyHostToDevice,
                                    b->stream));
-            MHIP(b, hipMemcpyAsync(tp + TP_BPI, g.bp_im.data(), g.bp_im.size() * sizeof(float), hipMemcpyHostToDevice,
+            STAGE_HIP(b, hipMemcpyAsync(tp + TP_BPI, g.bp_im.data(), g.bp_im.size() * sizeof(float), hipMemcpyHostToDevice,
                                    b->stream));
         }
     }
-    MHIP(b, hipStreamSynchronize(b->stream));             // the designs' host copies are read by now
+    STAGE_HIP(b, hipStreamSynchronize(b->stream));             // the designs' host copies are read by now
     for (auto &[k, g] : todo) {
         if (g.uf) commit_user_filter(&b->slots[k], g);
         if (g.bp) commit_band_pass(&b->slots[k], g);
@@ -1011,15 +958,13 @@ int rfa_demod_bank_create(int device, const int32_t *modes, int32_t n_channels, 
     if (!modes || n_channels < 1 || n_channels > RFA_DEMOD_BANK_MAX_CHANNELS) return RFA_ERR_INVALID;
     for (int32_t k = 0; k < n_channels; k++)
         if (!mode_ok(modes[k])) return RFA_ERR_INVALID;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0) return RFA_ERR_NODEVICE;
-    if (device < 0 || device >= count) return RFA_ERR_INVALID;
+    int rc = stage_check_device(device);
+    if (rc != RFA_OK) return rc;
     rfa_demod_bank *b = new (std::nothrow) rfa_demod_bank();
     if (!b) return RFA_ERR_NOMEM;
     const size_t K = (size_t)n_channels;
     b->device = device;
     b->K = n_channels;
-    int rc = RFA_OK;
     std::vector<float> t1, t2;
     if (!design_audio_filters(t1, t2)) rc = RFA_ERR_INVALID;
     b->slots.resize(K);
@@ -1030,9 +975,7 @@ int rfa_demod_bank_create(int device, const int32_t *modes, int32_t n_channels, 
         b->slots[k].a1_taps = t1;
         b->slots[k].a2_taps = t2;
     }
-    if (rc == RFA_OK && (hipSetDevice(device) != hipSuccess ||
-                         hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess))
-        rc = RFA_ERR_HIP;
+    if (rc == RFA_OK) rc = stage_open(b, device);
     if (rc == RFA_OK) {
         if (hipMalloc(&b->d_state, K * 2 * ST_SIZE * sizeof(float)) != hipSuccess ||
             hipMalloc(&b->d_taps, K * TP_SIZE * sizeof(float)) != hipSuccess ||
@@ -1066,21 +1009,18 @@ int rfa_demod_bank_create(int device, const int32_t *modes, int32_t n_channels, 
 
 int rfa_demod_bank_destroy(rfa_demod_bank *b) {
     if (!b) return RFA_ERR_INVALID;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    stage_close_stream(b);
     for (float *p : {b->d_state, b->d_taps, b->d_pre, b->d_pk, b->d_in, b->d_out})
         if (p) (void)hipFree(p);
     if (b->d_recs) (void)hipFree(b->d_recs);
     if (b->h_recs) (void)hipHostFree(b->h_recs);
     for (hipEvent_t e : b->ev)
         if (e) (void)hipEventDestroy(e);
-    hipStream_t own = b->own_stream ? b->own_stream : b->stream;
-    if (own) (void)hipStreamDestroy(own);
     delete b;
     return RFA_OK;
 }
 
-const char *rfa_demod_bank_last_error(const rfa_demod_bank *b) { return b ? b->err.c_str() : "null handle"; }
+const char *rfa_demod_bank_last_error(const rfa_demod_bank *b) { return stage_last_error(b); }
 
 int rfa_demod_bank_get_channels(const rfa_demod_bank *b, int32_t *n_channels) {
     if (!b || !n_channels) return RFA_ERR_INVALID;
@@ -1090,8 +1030,8 @@ int rfa_demod_bank_get_channels(const rfa_demod_bank *b, int32_t *n_channels) {
 
 int rfa_demod_bank_set_mode(rfa_demod_bank *b, int32_t k, int mode) {
     if (!b) return RFA_ERR_INVALID;
-    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
-    if (!mode_ok(mode)) return mfail(b, RFA_ERR_INVALID, "no such demodulation mode");
+    if (!slot_ok(b, k)) return stage_fail(b, RFA_ERR_INVALID, "no such slot");
+    if (!mode_ok(mode)) return stage_fail(b, RFA_ERR_INVALID, "no such demodulation mode");
     slot_set_mode(&b->slots[k], mode);
     return RFA_OK;
 }
@@ -1104,7 +1044,7 @@ int rfa_demod_bank_get_mode(const rfa_demod_bank *b, int32_t k, int32_t *mode) {
 
 int rfa_demod_bank_set_channel_width(rfa_demod_bank *b, int32_t k, int32_t w) {
     if (!b) return RFA_ERR_INVALID;
-    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    if (!slot_ok(b, k)) return stage_fail(b, RFA_ERR_INVALID, "no such slot");
     slot_set_width(&b->slots[k], w);
     return RFA_OK;
 }
@@ -1117,14 +1057,14 @@ int rfa_demod_bank_get_channel_width(const rfa_demod_bank *b, int32_t k, int32_t
 
 int rfa_demod_bank_set_volume(rfa_demod_bank *b, int32_t k, float v) {
     if (!b) return RFA_ERR_INVALID;
-    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    if (!slot_ok(b, k)) return stage_fail(b, RFA_ERR_INVALID, "no such slot");
     b->slots[k].volume = v;
     return RFA_OK;
 }
 
 int rfa_demod_bank_set_audio_sink(rfa_demod_bank *b, int32_t k, int enable) {
     if (!b) return RFA_ERR_INVALID;
-    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
+    if (!slot_ok(b, k)) return stage_fail(b, RFA_ERR_INVALID, "no such slot");
     b->slots[k].sink_enabled = enable != 0;
     return RFA_OK;
 }
@@ -1137,11 +1077,11 @@ int rfa_demod_bank_get_taps(const rfa_demod_bank *b, int32_t k, int which, float
 
 int rfa_demod_bank_get_state(rfa_demod_bank *b, int32_t k, float *last_max, float *carry_re, float *carry_im) {
     if (!b) return RFA_ERR_INVALID;
-    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
-    MHIP(b, hipSetDevice(b->device));
+    if (!slot_ok(b, k)) return stage_fail(b, RFA_ERR_INVALID, "no such slot");
+    STAGE_HIP(b, hipSetDevice(b->device));
     float s[3] = {0.0f, 0.0f, 0.0f};
-    MHIP(b, hipMemcpyAsync(s, bank_state(b, k, b->cur[k]) + ST_CARRY, sizeof s, hipMemcpyDeviceToHost, b->stream));
-    MHIP(b, hipStreamSynchronize(b->stream));
+    STAGE_HIP(b, hipMemcpyAsync(s, bank_state(b, k, b->cur[k]) + ST_CARRY, sizeof s, hipMemcpyDeviceToHost, b->stream));
+    STAGE_HIP(b, hipStreamSynchronize(b->stream));
     if (carry_re) *carry_re = s[0];
     if (carry_im) *carry_im = s[1];
     if (last_max) *last_max = s[2];
@@ -1150,9 +1090,9 @@ int rfa_demod_bank_get_state(rfa_demod_bank *b, int32_t k, float *last_max, floa
 
 int rfa_demod_bank_reset(rfa_demod_bank *b, int32_t k) {
     if (!b) return RFA_ERR_INVALID;
-    if (!slot_ok(b, k)) return mfail(b, RFA_ERR_INVALID, "no such slot");
-    MHIP(b, hipSetDevice(b->device));
-    MHIP(b, hipMemsetAsync(bank_state(b, k, b->cur[k]), 0, ST_SIZE * sizeof(float), b->stream));
+    if (!slot_ok(b, k)) return stage_fail(b, RFA_ERR_INVALID, "no such slot");
+    STAGE_HIP(b, hipSetDevice(b->device));
+    STAGE_HIP(b, hipMemsetAsync(bank_state(b, k, b->cur[k]), 0, ST_SIZE * sizeof(float), b->stream));
     forget_filters(&b->slots[k]);
     return RFA_OK;
 }
@@ -1178,9 +1118,9 @@ int rfa_demod_bank_process(rfa_demod_bank *b, const float *re, const float *im, 
     for (int k = 0; k < K; k++) n_audio[k] = 0;
     if (n_samples > (size_t)1 << 36 || packet_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40 ||
         audio_stride > (size_t)1 << 40)
-        return mfail(b, RFA_ERR_INVALID, "n_samples too large");
-    if (n_samples && (!re || !im)) return mfail(b, RFA_ERR_INVALID, "null input");
-    if (K > 1 && channel_stride < n_samples) return mfail(b, RFA_ERR_INVALID, "channel_stride below n_samples");
+        return stage_fail(b, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return stage_fail(b, RFA_ERR_INVALID, "null input");
+    if (K > 1 && channel_stride < n_samples) return stage_fail(b, RFA_ERR_INVALID, "channel_stride below n_samples");
     bank_plan(b, (long long)n_samples, (long long)packet_samples);
     long long max_npre = 0, max_audio = 0, max_pk = 0;
     bool any_on = false, any_agc = false;
@@ -1193,20 +1133,20 @@ int rfa_demod_bank_process(rfa_demod_bank *b, const float *re, const float *im, 
         max_audio = std::max(max_audio, p.n_audio);
         max_pk = std::max(max_pk, p.K);
     }
-    if ((size_t)max_audio > audio_stride) return mfail(b, RFA_ERR_SIZE, "audio_stride too small for a slot");
-    if (max_audio > 0 && !audio) return mfail(b, RFA_ERR_INVALID, "null output");
+    if ((size_t)max_audio > audio_stride) return stage_fail(b, RFA_ERR_SIZE, "audio_stride too small for a slot");
+    if (max_audio > 0 && !audio) return stage_fail(b, RFA_ERR_INVALID, "null output");
     if (max_pk > (long long)INT32_MAX || (max_npre + kTile - 1) / kTile > (long long)INT32_MAX)
-        return mfail(b, RFA_ERR_INVALID, "call too large for one grid");
+        return stage_fail(b, RFA_ERR_INVALID, "call too large for one grid");
     if (!any_on) return RFA_OK;
-    MHIP(b, hipSetDevice(b->device));
-    int rc = grow(b, b->d_pre, b->pre_cap, (size_t)K * (size_t)max_npre, "scratch");
-    if (rc == RFA_OK) rc = grow(b, b->d_pk, b->pk_cap, (size_t)K * 3 * (size_t)max_pk, "packet scratch");
+    STAGE_HIP(b, hipSetDevice(b->device));
+    int rc = stage_grow(b, b->d_pre, b->pre_cap, (size_t)K * (size_t)max_npre, "scratch");
+    if (rc == RFA_OK) rc = stage_grow(b, b->d_pk, b->pk_cap, (size_t)K * 3 * (size_t)max_pk, "packet scratch");
     if (rc == RFA_OK) rc = bank_rebuild(b);
     if (rc != RFA_OK) return rc;
 
     // this call's records: wait until the ring entry's previous copy has been made
     const int e = b->ring_at;
-    if (b->ev_used[e]) MHIP(b, hipEventSynchronize(b->ev[e]));
+    if (b->ev_used[e]) STAGE_HIP(b, hipEventSynchronize(b->ev[e]));
     DemodLaunch *recs = b->h_recs + (size_t)e * (size_t)K;
     const size_t pre_row = b->pre_cap / (size_t)K, pk_row = b->pk_cap / (size_t)K;
     for (int k = 0; k < K; k++) {
@@ -1228,27 +1168,27 @@ int rfa_demod_bank_process(rfa_demod_bank *b, const float *re, const float *im, 
         }
         recs[k] = a;
     }
-    MHIP(b, hipMemcpyAsync(b->d_recs, recs, (size_t)K * sizeof(DemodLaunch), hipMemcpyHostToDevice, b->stream));
-    MHIP(b, hipEventRecord(b->ev[e], b->stream));
+    STAGE_HIP(b, hipMemcpyAsync(b->d_recs, recs, (size_t)K * sizeof(DemodLaunch), hipMemcpyHostToDevice, b->stream));
+    STAGE_HIP(b, hipEventRecord(b->ev[e], b->stream));
     b->ev_used[e] = true;
     b->ring_at = (e + 1) % kRecRing;
 
     if (max_npre > 0) {
         hipLaunchKernelGGL(demod_bank_stage1_kernel, dim3((unsigned)((max_npre + kTile - 1) / kTile), (unsigned)K),
                            dim3(kTile), 0, b->stream, b->d_recs);
-        MHIP(b, hipGetLastError());
+        STAGE_HIP(b, hipGetLastError());
     }
     if (any_agc) {
         hipLaunchKernelGGL(demod_bank_packet_kernel, dim3((unsigned)max_pk, (unsigned)K), dim3(64), 0, b->stream,
                            b->d_recs);
-        MHIP(b, hipGetLastError());
+        STAGE_HIP(b, hipGetLastError());
     }
     hipLaunchKernelGGL(demod_bank_state_kernel, dim3((unsigned)K), dim3(kTile), 0, b->stream, b->d_recs);
-    MHIP(b, hipGetLastError());
+    STAGE_HIP(b, hipGetLastError());
     if (max_audio > 0) {
         hipLaunchKernelGGL(demod_bank_audio_kernel, dim3((unsigned)((max_audio + kTile - 1) / kTile), (unsigned)K),
                            dim3(kTile), 0, b->stream, b->d_recs);
-        MHIP(b, hipGetLastError());
+        STAGE_HIP(b, hipGetLastError());
     }
     for (int k = 0; k < K; k++) {
         if (b->slots[k].mode == RFA_DEMOD_OFF) continue;
@@ -1266,56 +1206,40 @@ int rfa_demod_bank_process_host(rfa_demod_bank *b, const float *re, const float 
     const size_t K = (size_t)b->K;
     for (size_t k = 0; k < K; k++) n_audio[k] = 0;
     if (n_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40 || audio_stride > (size_t)1 << 40)
-        return mfail(b, RFA_ERR_INVALID, "n_samples too large");
-    if (n_samples && (!re || !im)) return mfail(b, RFA_ERR_INVALID, "null input");
-    if (K > 1 && channel_stride < n_samples) return mfail(b, RFA_ERR_INVALID, "channel_stride below n_samples");
+        return stage_fail(b, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return stage_fail(b, RFA_ERR_INVALID, "null input");
+    if (K > 1 && channel_stride < n_samples) return stage_fail(b, RFA_ERR_INVALID, "channel_stride below n_samples");
     bank_plan(b, (long long)n_samples, (long long)packet_samples);
     size_t max_audio = 0;
     for (size_t k = 0; k < K; k++)
         if (b->slots[k].mode != RFA_DEMOD_OFF) max_audio = std::max(max_audio, (size_t)b->plans[k].n_audio);
-    if (max_audio > audio_stride) return mfail(b, RFA_ERR_SIZE, "audio_stride too small for a slot");
-    if (max_audio > 0 && !audio) return mfail(b, RFA_ERR_INVALID, "null output");
-    MHIP(b, hipSetDevice(b->device));
-    int rc = grow(b, b->d_in, b->d_in_cap, 2 * K * n_samples, "input staging");
-    if (rc == RFA_OK) rc = grow(b, b->d_out, b->d_out_cap, K * max_audio, "output staging");
+    if (max_audio > audio_stride) return stage_fail(b, RFA_ERR_SIZE, "audio_stride too small for a slot");
+    if (max_audio > 0 && !audio) return stage_fail(b, RFA_ERR_INVALID, "null output");
+    STAGE_HIP(b, hipSetDevice(b->device));
+    int rc = stage_grow(b, b->d_in, b->d_in_cap, 2 * K * n_samples, "input staging");
+    if (rc == RFA_OK) rc = stage_grow(b, b->d_out, b->d_out_cap, K * max_audio, "output staging");
     if (rc != RFA_OK) return rc;
     float *d_re = b->d_in, *d_im = b->d_in + K * n_samples;
     if (n_samples) {
         const size_t row = n_samples * sizeof(float), pitch = (K > 1 ? channel_stride : n_samples) * sizeof(float);
-        MHIP(b, hipMemcpy2DAsync(d_re, row, re, pitch, row, K, hipMemcpyHostToDevice, b->stream));
-        MHIP(b, hipMemcpy2DAsync(d_im, row, im, pitch, row, K, hipMemcpyHostToDevice, b->stream));
+        STAGE_HIP(b, hipMemcpy2DAsync(d_re, row, re, pitch, row, K, hipMemcpyHostToDevice, b->stream));
+        STAGE_HIP(b, hipMemcpy2DAsync(d_im, row, im, pitch, row, K, hipMemcpyHostToDevice, b->stream));
     }
     rc = rfa_demod_bank_process(b, d_re, d_im, n_samples, n_samples, packet_samples, b->d_out, max_audio, n_audio);
     if (rc != RFA_OK) return rc;
     for (size_t k = 0; k < K; k++)      // a slot's row of the caller's buffer is written up to its own count
         if (n_audio[k])
-            MHIP(b, hipMemcpyAsync(audio + k * audio_stride, b->d_out + k * max_audio, n_audio[k] * sizeof(float),
+            STAGE_HIP(b, hipMemcpyAsync(audio + k * audio_stride, b->d_out + k * max_audio, n_audio[k] * sizeof(float),
                                    hipMemcpyDeviceToHost, b->stream));
-    MHIP(b, hipStreamSynchronize(b->stream));
+    STAGE_HIP(b, hipStreamSynchronize(b->stream));
     return RFA_OK;
 }
 
-int rfa_demod_bank_set_stream(rfa_demod_bank *b, void *stream) {
-    if (!b) return RFA_ERR_INVALID;
-    // the carried state and the record ring are ordered on the bank's stream: drain it first
-    MHIP(b, hipSetDevice(b->device));
-    MHIP(b, hipStreamSynchronize(b->stream));
-    if (b->own_stream == nullptr) b->own_stream = b->stream;
-    b->stream = stream ? (hipStream_t)stream : b->own_stream;
-    return RFA_OK;
-}
+// (the record ring is ordered on the bank's stream too: stage_set_stream drains it)
+int rfa_demod_bank_set_stream(rfa_demod_bank *b, void *stream) { return stage_set_stream(b, stream); }
 
-int rfa_demod_bank_get_stream(const rfa_demod_bank *b, void **stream) {
-    if (!b || !stream) return RFA_ERR_INVALID;
-    *stream = (void *)b->stream;
-    return RFA_OK;
-}
+int rfa_demod_bank_get_stream(const rfa_demod_bank *b, void **stream) { return stage_get_stream(b, stream); }
 
-int rfa_demod_bank_synchronize(rfa_demod_bank *b) {
-    if (!b) return RFA_ERR_INVALID;
-    MHIP(b, hipSetDevice(b->device));
-    MHIP(b, hipStreamSynchronize(b->stream));
-    return RFA_OK;
-}
+int rfa_demod_bank_synchronize(rfa_demod_bank *b) { return stage_synchronize(b); }
 
 }  // extern "C"

@@ -47,6 +47,98 @@ FORMATS = {"s8": 0, "u8": 1, "s16": 2, "f32": 3}     # f32: already-mixed interl
 BYTES_PER_SAMPLE = {0: 2, 1: 2, 2: 4, 3: 8}
 
 
+def _format_id(input_format: str) -> int:
+    if input_format not in FORMATS:
+        raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
+    return FORMATS[input_format]
+
+
+def _raw_bytes(data) -> np.ndarray:
+    """Host bytes or any numpy array as one contiguous uint8 array."""
+    return np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview))
+                                else np.asarray(data).view(np.uint8).reshape(-1))
+
+
+class _Handle:
+    """A stage handle of the C-ABI: the entries ``{_prefix}_*`` on ``self._h``, with the lifetime
+    and stream methods that every stage has in the same form."""
+
+    _prefix = ""
+    _h = None
+    _stream = None            # what set_stream was last given (None: the handle's own stream)
+
+    def _create(self, entry: str, *args) -> None:
+        """``entry(*args, &handle)``: every create entry returns the handle through its last argument."""
+        h = _lib._h()
+        _lib.check(getattr(_lib.lib(), entry)(*args, ctypes.byref(h)), entry)
+        self._h = h
+
+    def __init_subclass__(cls, **kwargs):
+        super().__init_subclass__(**kwargs)
+        if "_prefix" in vars(cls):
+            cls._entries = {}     # name -> the bound C entry: a per-packet call looks nothing up twice
+
+    def _call(self, name: str, *args) -> None:
+        try:
+            fn = self._entries[name]
+        except KeyError:
+            fn = self._entries[name] = getattr(_lib.lib(), f"{self._prefix}_{name}")
+        status = fn(self._h, *args)
+        if status:
+            detail = (getattr(_lib.lib(), f"{self._prefix}_last_error")(self._h) or b"").decode()
+            raise _lib.RfaError(status, f"{self._prefix}_{name}", detail)
+
+    def _query_floats(self, name: str, n_arrays: int, n_ints: int, *pre):
+        """A size-then-fill getter ``name(*pre, float * x n_arrays, capacity, int32 * x n_ints)`` whose
+        first int32 is the arrays' length: (the arrays, the other int32 values)."""
+        ints = [ctypes.c_int32(0) for _ in range(n_ints)]
+        refs = [ctypes.byref(v) for v in ints]
+        self._call(name, *pre, *[None] * n_arrays, 0, *refs)
+        arrays = [np.empty(ints[0].value, np.float32) for _ in range(n_arrays)]
+        self._call(name, *pre, *[a.ctypes.data_as(_lib._fp) for a in arrays], ints[0].value, *refs)
+        return arrays, [v.value for v in ints[1:]]
+
+    def close(self) -> None:
+        if self._h:
+            getattr(_lib.lib(), f"{self._prefix}_destroy")(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def set_stream(self, stream_ptr: int | None) -> None:
+        """Enqueue on exactly this hipStream_t (None: the handle's own stream)."""
+        self._call("set_stream", stream_ptr or None)
+        self._stream = stream_ptr or None
+
+    def _follow_torch_stream(self, tensor) -> None:
+        """Move to torch's current stream on the tensor's device, so that a call is ordered after
+        the op that produced its inputs and before any later torch op that reads its outputs."""
+        import torch
+
+        cur = torch.cuda.current_stream(tensor.device).cuda_stream
+        if cur != self._stream:
+            self.set_stream(cur)
+
+    def synchronize(self) -> None:
+        self._call("synchronize")
+
+    @property
+    def stream(self) -> int:
+        s = _lib._vp()
+        self._call("get_stream", ctypes.byref(s))
+        return s.value or 0
+
+
 def create_low_pass_taps(gain: float, sample_rate: float, cutoff_frequency: float, transition_width: float,
                          attenuation_db: float, max_taps: int = 0) -> np.ndarray | None:
     """FirFilter.createLowPassTaps (dsp/FirFilter.kt:134-195), Blackman window; None where
@@ -64,7 +156,7 @@ def create_low_pass_taps(gain: float, sample_rate: float, cutoff_frequency: floa
     return taps
 
 
-class FrontEnd:
+class FrontEnd(_Handle):
     """One demodulated channel: mix + decimate raw IQ on ``device``.
 
     ``resampler=True`` filters with the live app's Resampler (analyzer/Resampler.kt:
@@ -74,90 +166,47 @@ class FrontEnd:
     (already-mixed interleaved floats: the Decimator alone, as ResamplerTest drives it).
     """
 
+    _prefix = "rfa_ddc"
+
     def __init__(self, input_format: str, sample_rate: int, output_sample_rate: int, device: int = 0,
                  resampler: bool = False, _fir=None):
-        if input_format not in FORMATS:
-            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
-        self.fmt = FORMATS[input_format]
+        self.fmt = _format_id(input_format)
         self.output_sample_rate = output_sample_rate
         self.resampler = resampler
-        self._stream = None
-        h = _lib._h()
         if _fir is not None:  # FirFilter(taps, decimation): see FirFilter below
             taps, decimation = _fir
             taps = np.ascontiguousarray(taps, np.float32)
-            _lib.check(_lib.lib().rfa_ddc_create_fir(device, self.fmt, sample_rate, taps.ctypes.data_as(_lib._fp),
-                                                     taps.size, decimation, ctypes.byref(h)), "rfa_ddc_create_fir")
+            self._create("rfa_ddc_create_fir", device, self.fmt, sample_rate, taps.ctypes.data_as(_lib._fp), taps.size,
+                         decimation)
         else:
-            create = _lib.lib().rfa_ddc_create_resampler if resampler else _lib.lib().rfa_ddc_create
-            _lib.check(create(device, self.fmt, sample_rate, output_sample_rate, ctypes.byref(h)),
-                       "rfa_ddc_create_resampler" if resampler else "rfa_ddc_create")
-        self._h = h
-
-    # -- lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _lib.lib().rfa_ddc_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    def _check(self, status: int, where: str) -> None:
-        if status != _lib.RFA_OK:
-            detail = (_lib.lib().rfa_ddc_last_error(self._h) or b"").decode()
-            raise _lib.RfaError(status, where, detail)
+            self._create("rfa_ddc_create_resampler" if resampler else "rfa_ddc_create", device, self.fmt, sample_rate,
+                         output_sample_rate)
 
     # -- configuration (IQConverter.setSampleRate / mixPacketIntoSamplePacket's table check)
     def set_sample_rate(self, sample_rate: int) -> None:
-        self._check(_lib.lib().rfa_ddc_set_sample_rate(self._h, sample_rate), "rfa_ddc_set_sample_rate")
+        self._call("set_sample_rate", sample_rate)
 
     def set_frequencies(self, frequency: int, channel_frequency: int) -> None:
-        self._check(_lib.lib().rfa_ddc_set_frequencies(self._h, frequency, channel_frequency),
-                    "rfa_ddc_set_frequencies")
+        self._call("set_frequencies", frequency, channel_frequency)
 
     @property
     def taps(self) -> np.ndarray:
-        n, d = ctypes.c_int32(0), ctypes.c_int32(0)
-        self._check(_lib.lib().rfa_ddc_get_taps(self._h, None, 0, ctypes.byref(n), ctypes.byref(d)), "get_taps")
-        out = np.empty(n.value, np.float32)
-        self._check(_lib.lib().rfa_ddc_get_taps(self._h, out.ctypes.data_as(_lib._fp), out.size, ctypes.byref(n),
-                                                ctypes.byref(d)), "get_taps")
-        return out
+        return self._query_floats("get_taps", 1, 2)[0][0]
 
     @property
     def decimation(self) -> int:
-        n, d = ctypes.c_int32(0), ctypes.c_int32(0)
-        self._check(_lib.lib().rfa_ddc_get_taps(self._h, None, 0, ctypes.byref(n), ctypes.byref(d)), "get_taps")
-        return d.value
+        return self.ratio()[1]
 
     def mixer(self):
         """(cos_t, sin_t, mix_frequency, cosine_index) of the current mixer table."""
-        n, mf, ci = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        L = _lib.lib()
-        self._check(L.rfa_ddc_get_mixer(self._h, None, None, 0, ctypes.byref(n), ctypes.byref(mf), ctypes.byref(ci)),
-                    "get_mixer")
-        c = np.empty(n.value, np.float32)
-        s = np.empty(n.value, np.float32)
-        self._check(L.rfa_ddc_get_mixer(self._h, c.ctypes.data_as(_lib._fp), s.ctypes.data_as(_lib._fp), c.size,
-                                        ctypes.byref(n), ctypes.byref(mf), ctypes.byref(ci)), "get_mixer")
-        return c, s, mf.value, ci.value
+        (c, s), (mf, ci) = self._query_floats("get_mixer", 2, 3)
+        return c, s, mf, ci
 
     def ratio(self):
         """(interpolation, decimation, taps per output) of the filter."""
-        i, d, t = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        self._check(_lib.lib().rfa_ddc_get_ratio(self._h, ctypes.byref(i), ctypes.byref(d), ctypes.byref(t)),
-                    "rfa_ddc_get_ratio")
-        return i.value, d.value, t.value
+        v = [ctypes.c_int32() for _ in range(3)]
+        self._call("get_ratio", *[ctypes.byref(x) for x in v])
+        return tuple(x.value for x in v)
 
     def max_outputs(self, n_samples: int) -> int:
         i, d, _ = self.ratio()
@@ -168,51 +217,30 @@ class FrontEnd:
         """Host bytes / numpy in -> (re, im) float32 numpy arrays of decimated samples."""
         if frequency is not None:
             self.set_frequencies(frequency, channel_frequency)
-        buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview))
-                                   else np.asarray(data).view(np.uint8).reshape(-1))
+        buf = _raw_bytes(data)
         n = buf.size // BYTES_PER_SAMPLE[self.fmt]
         cap = self.max_outputs(n)
         re = np.empty(cap, np.float32)
         im = np.empty(cap, np.float32)
         got = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_ddc_process_host(self._h, buf.ctypes.data, n, re.ctypes.data, im.ctypes.data, cap,
-                                                    ctypes.byref(got)), "rfa_ddc_process_host")
+        self._call("process_host", buf.ctypes.data, n, re.ctypes.data, im.ctypes.data, cap, ctypes.byref(got))
         return re[:got.value], im[:got.value]
 
     def process_device(self, in_ptr: int, n_samples: int, re_ptr: int, im_ptr: int, capacity: int) -> int:
         """Device pointers; asynchronous on the handle's stream; returns the output count."""
         got = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_ddc_process(self._h, in_ptr, n_samples, re_ptr, im_ptr, capacity,
-                                               ctypes.byref(got)), "rfa_ddc_process")
+        self._call("process", in_ptr, n_samples, re_ptr, im_ptr, capacity, ctypes.byref(got))
         return got.value
-
-    def set_stream(self, stream_ptr: int | None) -> None:
-        """Enqueue on exactly this hipStream_t (None: the handle's own stream)."""
-        self._check(_lib.lib().rfa_ddc_set_stream(self._h, stream_ptr or None), "rfa_ddc_set_stream")
-        self._stream = stream_ptr or None
 
     def process_tensor(self, raw, out_re, out_im) -> int:
         """torch.cuda tensors: raw bytes (uint8/int8/int16/float32, contiguous) -> planar float32 outputs.
         Runs on torch's current stream, so it is ordered after the op that produced ``raw``
         and before any later torch op that reads the outputs."""
-        import torch
-
-        cur = torch.cuda.current_stream(raw.device).cuda_stream
-        if cur != self._stream:
-            self.set_stream(cur)
+        self._follow_torch_stream(raw)
         n = raw.numel() * raw.element_size() // BYTES_PER_SAMPLE[self.fmt]
         if out_re.numel() != out_im.numel():
             raise ValueError("out_re and out_im must have the same length")
         return self.process_device(raw.data_ptr(), n, out_re.data_ptr(), out_im.data_ptr(), out_re.numel())
-
-    def synchronize(self) -> None:
-        self._check(_lib.lib().rfa_ddc_synchronize(self._h), "rfa_ddc_synchronize")
-
-    @property
-    def stream(self) -> int:
-        s = _lib._vp()
-        self._check(_lib.lib().rfa_ddc_get_stream(self._h, ctypes.byref(s)), "rfa_ddc_get_stream")
-        return s.value or 0
 
 
 class FirFilter(FrontEnd):
@@ -249,10 +277,8 @@ class FirFilter(FrontEnd):
 def mix_info(input_format: str, sample_rate: int, frequency: int, channel_frequency: int):
     """(folded mix frequency, mixer table length) that ``set_frequencies`` would build for one
     channel; length 0 is the empty table a ``FrontEndBank`` rejects.  Host-only."""
-    if input_format not in FORMATS:
-        raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
     mf, n = ctypes.c_int32(0), ctypes.c_int32(0)
-    _lib.check(_lib.lib().rfa_ddc_mix_info(FORMATS[input_format], sample_rate, frequency, channel_frequency,
+    _lib.check(_lib.lib().rfa_ddc_mix_info(_format_id(input_format), sample_rate, frequency, channel_frequency,
                                            ctypes.byref(mf), ctypes.byref(n)), "rfa_ddc_mix_info")
     return mf.value, n.value
 
@@ -272,55 +298,27 @@ def tile_plan(taps_per_output: int, interpolation: int, decimation: int, table_l
     return dict(zip(TILE_PLAN_FIELDS, (int(v) for v in out)))
 
 
-class FrontEndBank:
+class FrontEndBank(_Handle):
     """``n_channels`` channels out of one raw IQ stream per call (``rfa_ddc_bank_*``): the slots
     share format, rates and filter, each has its own mixer and delay line, and slot k gives
     bit for bit what a ``FrontEnd`` with the same arguments and calls gives.  One call is two
     kernel launches whatever the channel count (up to 256; two per 256 beyond).  A channel
     whose mixer table would be empty (``mix_info`` length 0) is rejected at ``set_frequencies``."""
 
+    _prefix = "rfa_ddc_bank"
+
     def __init__(self, input_format: str, sample_rate: int, output_sample_rate: int, n_channels: int,
                  device: int = 0, resampler: bool = False):
-        if input_format not in FORMATS:
-            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
-        self._h = None
-        self.fmt = FORMATS[input_format]
+        self.fmt = _format_id(input_format)
         self.output_sample_rate = output_sample_rate
         self.resampler = resampler
         self.n_channels = int(n_channels)
-        self._stream = None
-        h = _lib._h()
-        _lib.check(_lib.lib().rfa_ddc_bank_create(device, self.fmt, sample_rate, output_sample_rate,
-                                                  1 if resampler else 0, self.n_channels, ctypes.byref(h)),
-                   "rfa_ddc_bank_create")
-        self._h = h
-
-    # -- lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _lib.lib().rfa_ddc_bank_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    def _check(self, status: int, where: str) -> None:
-        if status != _lib.RFA_OK:
-            detail = (_lib.lib().rfa_ddc_bank_last_error(self._h) or b"").decode()
-            raise _lib.RfaError(status, where, detail)
+        self._create("rfa_ddc_bank_create", device, self.fmt, sample_rate, output_sample_rate, 1 if resampler else 0,
+                     self.n_channels)
 
     # -- configuration
     def set_sample_rate(self, sample_rate: int) -> None:
-        self._check(_lib.lib().rfa_ddc_bank_set_sample_rate(self._h, sample_rate), "rfa_ddc_bank_set_sample_rate")
+        self._call("set_sample_rate", sample_rate)
 
     def set_frequencies(self, frequency: int, channel_frequencies) -> None:
         """``FrontEnd.set_frequencies(frequency, channel_frequencies[k])`` on every slot, all or
@@ -329,90 +327,59 @@ class FrontEndBank:
         if len(ch) != self.n_channels:
             raise ValueError(f"{self.n_channels} channel frequencies expected, got {len(ch)}")
         arr = (ctypes.c_int64 * len(ch))(*ch)
-        self._check(_lib.lib().rfa_ddc_bank_set_frequencies(self._h, int(frequency), arr),
-                    "rfa_ddc_bank_set_frequencies")
+        self._call("set_frequencies", int(frequency), arr)
 
     def channel(self, k: int):
         """(mix_frequency, table_length, cosine_index) of slot k's mixer."""
         v = [ctypes.c_int32(0) for _ in range(3)]
-        self._check(_lib.lib().rfa_ddc_bank_get_channel(self._h, k, *[ctypes.byref(x) for x in v]),
-                    "rfa_ddc_bank_get_channel")
+        self._call("get_channel", k, *[ctypes.byref(x) for x in v])
         return tuple(x.value for x in v)
 
     @property
     def taps(self) -> np.ndarray:
-        n, d = ctypes.c_int32(0), ctypes.c_int32(0)
-        L = _lib.lib()
-        self._check(L.rfa_ddc_bank_get_taps(self._h, None, 0, ctypes.byref(n), ctypes.byref(d)), "get_taps")
-        out = np.empty(n.value, np.float32)
-        self._check(L.rfa_ddc_bank_get_taps(self._h, out.ctypes.data_as(_lib._fp), out.size, ctypes.byref(n),
-                                            ctypes.byref(d)), "get_taps")
-        return out
+        return self._query_floats("get_taps", 1, 2)[0][0]
 
     def ratio(self):
         """(interpolation, decimation, taps per output) of the shared filter."""
-        i, d, t = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        self._check(_lib.lib().rfa_ddc_bank_get_ratio(self._h, ctypes.byref(i), ctypes.byref(d), ctypes.byref(t)),
-                    "rfa_ddc_bank_get_ratio")
-        return i.value, d.value, t.value
+        v = [ctypes.c_int32() for _ in range(3)]
+        self._call("get_ratio", *[ctypes.byref(x) for x in v])
+        return tuple(x.value for x in v)
 
     def max_outputs(self, n_samples: int) -> int:
         """Upper bound of one call's outputs per channel."""
         n = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_ddc_bank_max_outputs(self._h, n_samples, ctypes.byref(n)),
-                    "rfa_ddc_bank_max_outputs")
+        self._call("max_outputs", n_samples, ctypes.byref(n))
         return n.value
 
     # -- processing
     def process(self, data):
         """Host bytes / numpy in -> (re[K, n], im[K, n]) float32 numpy arrays."""
-        buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview))
-                                   else np.asarray(data).view(np.uint8).reshape(-1))
+        buf = _raw_bytes(data)
         n = buf.size // BYTES_PER_SAMPLE[self.fmt]
         cap = self.max_outputs(n)
         re = np.empty((self.n_channels, cap), np.float32)
         im = np.empty((self.n_channels, cap), np.float32)
         got = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_ddc_bank_process_host(self._h, buf.ctypes.data, n, re.ctypes.data, im.ctypes.data,
-                                                         cap, ctypes.byref(got)), "rfa_ddc_bank_process_host")
+        self._call("process_host", buf.ctypes.data, n, re.ctypes.data, im.ctypes.data, cap, ctypes.byref(got))
         return re[:, :got.value], im[:, :got.value]
 
     def process_device(self, in_ptr: int, n_samples: int, re_ptr: int, im_ptr: int, channel_stride: int) -> int:
         """Device pointers, outputs [K][channel_stride] floats; asynchronous on the bank's stream;
         returns the output count per channel."""
         got = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_ddc_bank_process(self._h, in_ptr, n_samples, re_ptr, im_ptr, channel_stride,
-                                                    ctypes.byref(got)), "rfa_ddc_bank_process")
+        self._call("process", in_ptr, n_samples, re_ptr, im_ptr, channel_stride, ctypes.byref(got))
         return got.value
 
     def process_tensor(self, raw, out_re, out_im) -> int:
         """torch.cuda tensors: raw bytes (contiguous) -> float32 outputs of shape [K, stride], on
         torch's current stream (see ``FrontEnd.process_tensor``)."""
-        import torch
-
-        cur = torch.cuda.current_stream(raw.device).cuda_stream
-        if cur != self._stream:
-            self.set_stream(cur)
+        self._follow_torch_stream(raw)
         n = raw.numel() * raw.element_size() // BYTES_PER_SAMPLE[self.fmt]
         if out_re.shape != out_im.shape or out_re.dim() != 2 or out_re.shape[0] != self.n_channels:
             raise ValueError(f"out_re and out_im must both have shape [{self.n_channels}, stride]")
         if not (out_re.is_contiguous() and out_im.is_contiguous()):
             raise ValueError("out_re and out_im must be contiguous")
         return self.process_device(raw.data_ptr(), n, out_re.data_ptr(), out_im.data_ptr(), out_re.shape[1])
-
-    def set_stream(self, stream_ptr: int | None) -> None:
-        """Enqueue on exactly this hipStream_t (None: the bank's own stream)."""
-        self._check(_lib.lib().rfa_ddc_bank_set_stream(self._h, stream_ptr or None), "rfa_ddc_bank_set_stream")
-        self._stream = stream_ptr or None
-
-    def synchronize(self) -> None:
-        self._check(_lib.lib().rfa_ddc_bank_synchronize(self._h), "rfa_ddc_bank_synchronize")
-
-    @property
-    def stream(self) -> int:
-        s = _lib._vp()
-        self._check(_lib.lib().rfa_ddc_bank_get_stream(self._h, ctypes.byref(s)), "rfa_ddc_bank_get_stream")
-        return s.value or 0
 
 
 # ---------------------------------------------------------------- demodulator proper
@@ -456,7 +423,7 @@ def create_band_pass_taps(gain: float, sample_rate: float, low_cutoff: float, hi
     return re, im
 
 
-class Demodulator:
+class Demodulator(_Handle):
     """analyzer/Demodulator.kt with its AudioSink on ``device``: quadrature-rate planar IQ
     in, 48 kHz float audio out (``rfanalyzer_amd/csrc/demod.hip`` through ``rfa_demod_*``).
 
@@ -467,58 +434,33 @@ class Demodulator:
     packet by packet.  ``audio_sink=False`` returns the demodulator's own audio buffer at the
     packet rate instead of the AudioSink's 48 kHz stream."""
 
+    _prefix = "rfa_demod"
+
     def __init__(self, mode="off", device: int = 0, audio_sink: bool = True):
-        self._h = None
-        self._stream = None
-        h = _lib._h()
-        _lib.check(_lib.lib().rfa_demod_create(device, _mode_id(mode), ctypes.byref(h)), "rfa_demod_create")
-        self._h = h
+        self._create("rfa_demod_create", device, _mode_id(mode))
         if not audio_sink:
             self.audio_sink = False
-
-    # -- lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _lib.lib().rfa_demod_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    def _check(self, status: int, where: str) -> None:
-        if status != _lib.RFA_OK:
-            detail = (_lib.lib().rfa_demod_last_error(self._h) or b"").decode()
-            raise _lib.RfaError(status, where, detail)
 
     # -- the Kotlin properties
     @property
     def demodulationMode(self) -> int:  # noqa: N802
         m = ctypes.c_int32(0)
-        self._check(_lib.lib().rfa_demod_get_mode(self._h, ctypes.byref(m)), "rfa_demod_get_mode")
+        self._call("get_mode", ctypes.byref(m))
         return m.value
 
     @demodulationMode.setter
     def demodulationMode(self, mode) -> None:  # noqa: N802
-        self._check(_lib.lib().rfa_demod_set_mode(self._h, _mode_id(mode)), "rfa_demod_set_mode")
+        self._call("set_mode", _mode_id(mode))
 
     @property
     def channelWidth(self) -> int:  # noqa: N802
         w = ctypes.c_int32(0)
-        self._check(_lib.lib().rfa_demod_get_channel_width(self._h, ctypes.byref(w)), "rfa_demod_get_channel_width")
+        self._call("get_channel_width", ctypes.byref(w))
         return w.value
 
     @channelWidth.setter
     def channelWidth(self, width: int) -> None:  # noqa: N802
-        self._check(_lib.lib().rfa_demod_set_channel_width(self._h, int(width)), "rfa_demod_set_channel_width")
+        self._call("set_channel_width", int(width))
 
     @property
     def audioVolumeLevel(self) -> float:  # noqa: N802
@@ -526,7 +468,7 @@ class Demodulator:
 
     @audioVolumeLevel.setter
     def audioVolumeLevel(self, v: float) -> None:  # noqa: N802
-        self._check(_lib.lib().rfa_demod_set_volume(self._h, float(v)), "rfa_demod_set_volume")
+        self._call("set_volume", float(v))
         self._volume = float(np.float32(v))
 
     @property
@@ -535,7 +477,7 @@ class Demodulator:
 
     @audio_sink.setter
     def audio_sink(self, enable: bool) -> None:
-        self._check(_lib.lib().rfa_demod_set_audio_sink(self._h, 1 if enable else 0), "rfa_demod_set_audio_sink")
+        self._call("set_audio_sink", 1 if enable else 0)
         self._sink = bool(enable)
 
     @property
@@ -546,29 +488,21 @@ class Demodulator:
     def taps(self, which: str):
         """("user" | "bandpass" | "audio1" | "audio2") -> (re, im, decimation); empty before a
         packet has built the user or band-pass filter."""
-        n, d = ctypes.c_int32(0), ctypes.c_int32(0)
-        L = _lib.lib()
-        self._check(L.rfa_demod_get_taps(self._h, TAPS[which], None, None, 0, ctypes.byref(n), ctypes.byref(d)),
-                    "rfa_demod_get_taps")
-        re = np.empty(n.value, np.float32)
-        im = np.empty(n.value, np.float32)
-        self._check(L.rfa_demod_get_taps(self._h, TAPS[which], re.ctypes.data_as(_lib._fp),
-                                         im.ctypes.data_as(_lib._fp), re.size, ctypes.byref(n), ctypes.byref(d)),
-                    "rfa_demod_get_taps")
-        return re, im, d.value
+        (re, im), (d,) = self._query_floats("get_taps", 2, 2, TAPS[which])
+        return re, im, d
 
     def state(self):
         """(lastMax, carryOverSamplesRe, carryOverSamplesIm) as numpy float32; drains the stream."""
         v = [ctypes.c_float(0) for _ in range(3)]
-        self._check(_lib.lib().rfa_demod_get_state(self._h, *[ctypes.byref(x) for x in v]), "rfa_demod_get_state")
+        self._call("get_state", *[ctypes.byref(x) for x in v])
         return tuple(np.float32(x.value) for x in v)
 
     def reset(self) -> None:
-        self._check(_lib.lib().rfa_demod_reset(self._h), "rfa_demod_reset")
+        self._call("reset")
 
     def max_outputs(self, n_samples: int) -> int:
         n = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_demod_max_outputs(self._h, n_samples, ctypes.byref(n)), "rfa_demod_max_outputs")
+        self._call("max_outputs", n_samples, ctypes.byref(n))
         return n.value
 
     # -- processing
@@ -581,48 +515,28 @@ class Demodulator:
         cap = self.max_outputs(re.size)
         out = np.empty(max(cap, 1), np.float32)
         got = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_demod_process_host(self._h, re.ctypes.data, im.ctypes.data, re.size,
-                                                      packet_samples or 0, out.ctypes.data, cap, ctypes.byref(got)),
-                    "rfa_demod_process_host")
+        self._call("process_host", re.ctypes.data, im.ctypes.data, re.size, packet_samples or 0, out.ctypes.data, cap,
+                   ctypes.byref(got))
         return out[:got.value].copy()
 
     def process_device(self, re_ptr: int, im_ptr: int, n_samples: int, audio_ptr: int, capacity: int,
                        packet_samples: int | None = None) -> int:
         """Device pointers; asynchronous on the handle's stream; returns the audio sample count."""
         got = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_demod_process(self._h, re_ptr, im_ptr, n_samples, packet_samples or 0, audio_ptr,
-                                                 capacity, ctypes.byref(got)), "rfa_demod_process")
+        self._call("process", re_ptr, im_ptr, n_samples, packet_samples or 0, audio_ptr, capacity, ctypes.byref(got))
         return got.value
-
-    def set_stream(self, stream_ptr: int | None) -> None:
-        """Enqueue on exactly this hipStream_t (None: the handle's own stream)."""
-        self._check(_lib.lib().rfa_demod_set_stream(self._h, stream_ptr or None), "rfa_demod_set_stream")
-        self._stream = stream_ptr or None
 
     def process_tensor(self, re, im, out, packet_samples: int | None = None) -> int:
         """torch.cuda float32 tensors; runs on torch's current stream, ordered after the op that
         produced ``re``/``im`` and before any later torch op that reads ``out``."""
-        import torch
-
-        cur = torch.cuda.current_stream(re.device).cuda_stream
-        if cur != self._stream:
-            self.set_stream(cur)
+        self._follow_torch_stream(re)
         if re.numel() != im.numel():
             raise ValueError("re and im must have the same length")
         return self.process_device(re.data_ptr(), im.data_ptr(), re.numel(), out.data_ptr(), out.numel(),
                                    packet_samples)
 
-    def synchronize(self) -> None:
-        self._check(_lib.lib().rfa_demod_synchronize(self._h), "rfa_demod_synchronize")
 
-    @property
-    def stream(self) -> int:
-        s = _lib._vp()
-        self._check(_lib.lib().rfa_demod_get_stream(self._h, ctypes.byref(s)), "rfa_demod_get_stream")
-        return s.value or 0
-
-
-class DemodulatorBank:
+class DemodulatorBank(_Handle):
     """``len(modes)`` demodulators, each with its AudioSink, in one handle (``rfa_demod_bank_*``):
     one stream and one set of launches -- four kernels and one copy of the slots' launch
     records per call, whatever the slot count.  Slot k gives bit for bit what a ``Demodulator``
@@ -630,96 +544,59 @@ class DemodulatorBank:
     Modes of different quadrature rates may share a bank; an "off" slot returns no audio and
     keeps its state."""
 
+    _prefix = "rfa_demod_bank"
+
     def __init__(self, modes, device: int = 0, audio_sink: bool = True):
-        self._h = None
-        self._stream = None
         ids = [_mode_id(m) for m in modes]
         self.n_channels = len(ids)
-        h = _lib._h()
         arr = (ctypes.c_int32 * max(len(ids), 1))(*ids)
-        _lib.check(_lib.lib().rfa_demod_bank_create(device, arr, len(ids), ctypes.byref(h)), "rfa_demod_bank_create")
-        self._h = h
+        self._create("rfa_demod_bank_create", device, arr, len(ids))
         self._counts = (ctypes.c_size_t * self.n_channels)()
         if not audio_sink:
             for k in range(self.n_channels):
                 self.set_audio_sink(k, False)
 
-    # -- lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _lib.lib().rfa_demod_bank_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    def _check(self, status: int, where: str) -> None:
-        if status != _lib.RFA_OK:
-            detail = (_lib.lib().rfa_demod_bank_last_error(self._h) or b"").decode()
-            raise _lib.RfaError(status, where, detail)
-
     # -- per slot, as the Demodulator's properties
     def mode(self, k: int) -> int:
         m = ctypes.c_int32(0)
-        self._check(_lib.lib().rfa_demod_bank_get_mode(self._h, k, ctypes.byref(m)), "rfa_demod_bank_get_mode")
+        self._call("get_mode", k, ctypes.byref(m))
         return m.value
 
     def set_mode(self, k: int, mode) -> None:
-        self._check(_lib.lib().rfa_demod_bank_set_mode(self._h, k, _mode_id(mode)), "rfa_demod_bank_set_mode")
+        self._call("set_mode", k, _mode_id(mode))
 
     def channel_width(self, k: int) -> int:
         w = ctypes.c_int32(0)
-        self._check(_lib.lib().rfa_demod_bank_get_channel_width(self._h, k, ctypes.byref(w)),
-                    "rfa_demod_bank_get_channel_width")
+        self._call("get_channel_width", k, ctypes.byref(w))
         return w.value
 
     def set_channel_width(self, k: int, width: int) -> None:
-        self._check(_lib.lib().rfa_demod_bank_set_channel_width(self._h, k, int(width)),
-                    "rfa_demod_bank_set_channel_width")
+        self._call("set_channel_width", k, int(width))
 
     def set_volume(self, k: int, v: float) -> None:
-        self._check(_lib.lib().rfa_demod_bank_set_volume(self._h, k, float(v)), "rfa_demod_bank_set_volume")
+        self._call("set_volume", k, float(v))
 
     def set_audio_sink(self, k: int, on: bool) -> None:
-        self._check(_lib.lib().rfa_demod_bank_set_audio_sink(self._h, k, 1 if on else 0),
-                    "rfa_demod_bank_set_audio_sink")
+        self._call("set_audio_sink", k, 1 if on else 0)
 
     def taps(self, k: int, which: str):
         """Slot k's ("user" | "bandpass" | "audio1" | "audio2") -> (re, im, decimation)."""
-        n, d = ctypes.c_int32(0), ctypes.c_int32(0)
-        L = _lib.lib()
-        self._check(L.rfa_demod_bank_get_taps(self._h, k, TAPS[which], None, None, 0, ctypes.byref(n),
-                                              ctypes.byref(d)), "rfa_demod_bank_get_taps")
-        re = np.empty(n.value, np.float32)
-        im = np.empty(n.value, np.float32)
-        self._check(L.rfa_demod_bank_get_taps(self._h, k, TAPS[which], re.ctypes.data_as(_lib._fp),
-                                              im.ctypes.data_as(_lib._fp), re.size, ctypes.byref(n), ctypes.byref(d)),
-                    "rfa_demod_bank_get_taps")
-        return re, im, d.value
+        (re, im), (d,) = self._query_floats("get_taps", 2, 2, k, TAPS[which])
+        return re, im, d
 
     def state(self, k: int):
         """Slot k's (lastMax, carryOverSamplesRe, carryOverSamplesIm); drains the stream."""
         v = [ctypes.c_float(0) for _ in range(3)]
-        self._check(_lib.lib().rfa_demod_bank_get_state(self._h, k, *[ctypes.byref(x) for x in v]),
-                    "rfa_demod_bank_get_state")
+        self._call("get_state", k, *[ctypes.byref(x) for x in v])
         return tuple(np.float32(x.value) for x in v)
 
     def reset(self, k: int) -> None:
-        self._check(_lib.lib().rfa_demod_bank_reset(self._h, k), "rfa_demod_bank_reset")
+        self._call("reset", k)
 
     def max_outputs(self, n_samples: int) -> list[int]:
         """Every slot's audio sample count for the next call of ``n_samples``."""
         n = (ctypes.c_size_t * self.n_channels)()
-        self._check(_lib.lib().rfa_demod_bank_max_outputs(self._h, n_samples, n), "rfa_demod_bank_max_outputs")
+        self._call("max_outputs", n_samples, n)
         return list(n)
 
     # -- processing
@@ -732,34 +609,23 @@ class DemodulatorBank:
         n = re.shape[1]
         cap = max(self.max_outputs(n))
         out = np.empty((self.n_channels, max(cap, 1)), np.float32)
-        self._check(_lib.lib().rfa_demod_bank_process_host(self._h, re.ctypes.data, im.ctypes.data, n, n,
-                                                           packet_samples or 0, out.ctypes.data, out.shape[1],
-                                                           self._counts), "rfa_demod_bank_process_host")
+        self._call("process_host", re.ctypes.data, im.ctypes.data, n, n, packet_samples or 0, out.ctypes.data,
+                   out.shape[1], self._counts)
         return [out[k, :g].copy() for k, g in enumerate(self._counts)]
 
     def process_device(self, re_ptr: int, im_ptr: int, channel_stride: int, n_samples: int, audio_ptr: int,
                        audio_stride: int, packet_samples: int | None = None) -> list[int]:
         """Device pointers, rows ``channel_stride`` / ``audio_stride`` floats apart; asynchronous on
         the bank's stream; returns every slot's audio sample count."""
-        self._check(_lib.lib().rfa_demod_bank_process(self._h, re_ptr, im_ptr, channel_stride, n_samples,
-                                                      packet_samples or 0, audio_ptr, audio_stride, self._counts),
-                    "rfa_demod_bank_process")
+        self._call("process", re_ptr, im_ptr, channel_stride, n_samples, packet_samples or 0, audio_ptr, audio_stride,
+                   self._counts)
         return list(self._counts)
-
-    def set_stream(self, stream_ptr: int | None) -> None:
-        """Enqueue on exactly this hipStream_t (None: the bank's own stream)."""
-        self._check(_lib.lib().rfa_demod_bank_set_stream(self._h, stream_ptr or None), "rfa_demod_bank_set_stream")
-        self._stream = stream_ptr or None
 
     def process_tensor(self, re, im, out, packet_samples: int | None = None) -> list[int]:
         """torch.cuda float32 tensors [K, n] (rows may be slices of wider tensors: unit stride
         along n) -> ``out`` [K, capacity]; on torch's current stream (see
         ``Demodulator.process_tensor``)."""
-        import torch
-
-        cur = torch.cuda.current_stream(re.device).cuda_stream
-        if cur != self._stream:
-            self.set_stream(cur)
+        self._follow_torch_stream(re)
         K = self.n_channels
         if re.shape != im.shape or re.dim() != 2 or re.shape[0] != K or out.dim() != 2 or out.shape[0] != K:
             raise ValueError(f"re, im and out must have shape [{K}, .]")
@@ -778,17 +644,38 @@ class DemodulatorBank:
         return self.process_device(re.data_ptr(), im.data_ptr(), stride, re.shape[1], out.data_ptr(), ostride,
                                    packet_samples)
 
-    def synchronize(self) -> None:
-        self._check(_lib.lib().rfa_demod_bank_synchronize(self._h), "rfa_demod_bank_synchronize")
+
+class _Chain:
+    """What the receiver chains share: the context manager, the audio tensor and the staging of
+    one host packet.  A chain has ``front``, ``_buffers``, ``process_device`` and ``close``."""
+
+    _raw = _re = _im = _audio = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     @property
-    def stream(self) -> int:
-        s = _lib._vp()
-        self._check(_lib.lib().rfa_demod_bank_get_stream(self._h, ctypes.byref(s)), "rfa_demod_bank_get_stream")
-        return s.value or 0
+    def audio_tensor(self):
+        return self._audio
+
+    def _process_host(self, raw_bytes, demod):
+        """One raw input packet (host bytes) through ``process_device``, waited for on ``demod``."""
+        torch = self._torch
+        buf = _raw_bytes(raw_bytes)
+        n = buf.size // BYTES_PER_SAMPLE[self.front.fmt]
+        self._buffers(buf.size, n)
+        demod.synchronize()                           # the staging buffer's previous use is over
+        self._raw[:buf.size].copy_(torch.from_numpy(buf.copy()))
+        torch.cuda.synchronize(self._tdev)
+        got = self.process_device(self._raw.data_ptr(), n)
+        demod.synchronize()
+        return got
 
 
-class Receiver:
+class Receiver(_Chain):
     """Raw IQ bytes -> audio: ``FrontEnd(..., resampler=True)`` at the mode's quadrature rate
     chained into a ``Demodulator``, device to device on one stream.  One ``process`` call is
     one input packet, as the app's Scheduler feeds its Demodulator.  Changing ``mode`` retunes
@@ -806,7 +693,6 @@ class Receiver:
         self.demod = Demodulator(mode, device)
         self.front = None
         self._freqs = None
-        self._raw = self._re = self._im = self._audio = None
         self._cap_for = (None, 0)
         self._retune()
 
@@ -859,23 +745,9 @@ class Receiver:
         nq = self.front.process_device(raw_ptr, n_samples, self._re.data_ptr(), self._im.data_ptr(), cap)
         return self.demod.process_device(self._re.data_ptr(), self._im.data_ptr(), nq, self._audio.data_ptr(), cap)
 
-    @property
-    def audio_tensor(self):
-        return self._audio
-
     def process(self, raw_bytes) -> np.ndarray:
         """One raw input packet (host bytes) -> float32 audio."""
-        torch = self._torch
-        buf = np.ascontiguousarray(np.frombuffer(raw_bytes, np.uint8)
-                                   if isinstance(raw_bytes, (bytes, bytearray, memoryview))
-                                   else np.asarray(raw_bytes).view(np.uint8).reshape(-1))
-        n = buf.size // BYTES_PER_SAMPLE[self.front.fmt]
-        self._buffers(buf.size, n)
-        self.demod.synchronize()                      # the staging buffer's previous use is over
-        self._raw[:buf.size].copy_(torch.from_numpy(buf.copy()))
-        torch.cuda.synchronize(self._tdev)
-        got = self.process_device(self._raw.data_ptr(), n)
-        self.demod.synchronize()
+        got = self._process_host(raw_bytes, self.demod)
         return self._audio[:got].cpu().numpy()
 
     def close(self) -> None:
@@ -884,42 +756,36 @@ class Receiver:
             self.front = None
         self.demod.close()
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *exc):
-        self.close()
+def _common_rate(modes):
+    """(the modes as a list, their one quadrature rate): a bank chain's slots share the front end."""
+    modes = list(modes)
+    if not modes:
+        raise ValueError("at least one mode")
+    rates = {mode_info(m)[0] for m in modes}
+    if len(rates) != 1:
+        raise ValueError(f"the modes' quadrature rates differ: {sorted(rates)}")
+    return modes, rates.pop()
 
 
-class ReceiverBank:
-    """Raw IQ bytes -> one audio stream per channel: a ``FrontEndBank(..., resampler=True)`` at
-    the modes' quadrature rate feeding a ``DemodulatorBank``, device to device on one stream.
-    Slot k's audio equals, bit for bit, a ``Receiver`` in mode ``modes[k]`` tuned to channel k
-    and given the same packets.  The slots share the resampler, so every mode must have the
-    same quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``).
-    Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
+class _BankChain(_Chain):
+    """Raw IQ bytes -> one audio stream per slot: a banked front end at the modes' common
+    quadrature rate feeding a ``DemodulatorBank``, device to device on one stream.  A subclass
+    supplies ``_make_front(*front_args)`` and ``_capacity(n)``, the rows' length for a call of n
+    samples."""
 
-    def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0):
+    def __init__(self, input_format: str, sample_rate: int, modes, rate: int, device: int, *front_args):
         import torch
 
-        modes = list(modes)
-        if not modes:
-            raise ValueError("at least one mode")
-        rates = {mode_info(m)[0] for m in modes}
-        if len(rates) != 1:
-            raise ValueError(f"the modes' quadrature rates differ: {sorted(rates)}")
         self._torch = torch
         self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
         self._tdev = torch.device("cuda", device)
-        self.quadrature_rate = rates.pop()
+        self.quadrature_rate = rate
         self.demods, self.front = None, None
         self._n_channels = len(modes)
-        self._raw = self._re = self._im = self._audio = None
-        self._cap_for = (None, 0)
         try:
             self.demods = DemodulatorBank(modes, device)
-            self.front = FrontEndBank(input_format, self.sample_rate, self.quadrature_rate, len(modes), device,
-                                      resampler=True)
+            self.front = self._make_front(*front_args)
             self.set_stream(None)
         except Exception:
             self.close()
@@ -939,9 +805,6 @@ class ReceiverBank:
                              f"{self.quadrature_rate}")
         self.demods.set_mode(k, mode)
 
-    def set_frequencies(self, frequency: int, channel_frequencies) -> None:
-        self.front.set_frequencies(frequency, channel_frequencies)
-
     def set_stream(self, stream_ptr: int | None) -> None:
         """Enqueue every stage on exactly this hipStream_t (None: the demodulator bank's own)."""
         self.demods.set_stream(stream_ptr)
@@ -954,9 +817,7 @@ class ReceiverBank:
         torch = self._torch
         if self._raw is None or self._raw.numel() < nbytes:
             self._raw = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self._tdev)
-        if self._cap_for[0] != n:
-            self._cap_for = (n, self.front.max_outputs(n))
-        cap = self._cap_for[1]
+        cap = self._capacity(n)
         if self._re is None or self._re.shape[1] < cap:
             shape = (self.n_channels, cap)
             self._re = torch.empty(shape, dtype=torch.float32, device=self._tdev)
@@ -972,23 +833,9 @@ class ReceiverBank:
         return self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq, self._audio.data_ptr(),
                                           cap)
 
-    @property
-    def audio_tensor(self):
-        return self._audio
-
     def process(self, raw_bytes) -> list[np.ndarray]:
         """One raw input packet (host bytes) -> K float32 audio arrays."""
-        torch = self._torch
-        buf = np.ascontiguousarray(np.frombuffer(raw_bytes, np.uint8)
-                                   if isinstance(raw_bytes, (bytes, bytearray, memoryview))
-                                   else np.asarray(raw_bytes).view(np.uint8).reshape(-1))
-        n = buf.size // BYTES_PER_SAMPLE[self.front.fmt]
-        self._buffers(buf.size, n)
-        self.synchronize()                            # the staging buffer's previous use is over
-        self._raw[:buf.size].copy_(torch.from_numpy(buf.copy()))
-        torch.cuda.synchronize(self._tdev)
-        got = self.process_device(self._raw.data_ptr(), n)
-        self.synchronize()
+        got = self._process_host(raw_bytes, self.demods)
         audio = self._audio.cpu().numpy()
         return [audio[k, :g].copy() for k, g in enumerate(got)]
 
@@ -1000,16 +847,35 @@ class ReceiverBank:
             self.demods.close()
             self.demods = None
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *exc):
-        self.close()
+class ReceiverBank(_BankChain):
+    """Raw IQ bytes -> one audio stream per channel: a ``FrontEndBank(..., resampler=True)`` at
+    the modes' quadrature rate feeding a ``DemodulatorBank``, device to device on one stream.
+    Slot k's audio equals, bit for bit, a ``Receiver`` in mode ``modes[k]`` tuned to channel k
+    and given the same packets.  The slots share the resampler, so every mode must have the
+    same quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``).
+    Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
+
+    def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0):
+        self._cap_for = (None, 0)
+        super().__init__(input_format, sample_rate, *_common_rate(modes), device)
+
+    def _make_front(self):
+        return FrontEndBank(self.input_format, self.sample_rate, self.quadrature_rate, self.n_channels, self.device,
+                            resampler=True)
+
+    def _capacity(self, n: int) -> int:
+        if self._cap_for[0] != n:
+            self._cap_for = (n, self.front.max_outputs(n))
+        return self._cap_for[1]
+
+    def set_frequencies(self, frequency: int, channel_frequencies) -> None:
+        self.front.set_frequencies(frequency, channel_frequencies)
 
 
 # ---------------------------------------------------------------- polyphase channelizer
 
-class Channelizer:
+class Channelizer(_Handle):
     """All ``n_channels`` = M channels of the uniform raster k * Fs / M out of one raw IQ stream
     per call (``rfa_pfb_*``, ``rfanalyzer_amd/csrc/channelizer.hip``): the prototype low-pass
     ``taps`` is folded once per output time and one M-point DFT gives every channel, so a call
@@ -1020,21 +886,21 @@ class Channelizer:
     what ``DemodulatorBank.process_device`` reads.  Channels that are not on a raster stay with
     ``FrontEndBank``."""
 
-    def __init__(self, input_format: str, n_channels: int, decimation: int, taps, device: int = 0):
-        if input_format not in FORMATS:
-            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
-        self._h = None
-        self.fmt = FORMATS[input_format]
+    _prefix = "rfa_pfb"
+
+    def __init__(self, input_format: str, n_channels: int, decimation: int, taps, device: int = 0,
+                 _interpolation: int | None = None):
+        self.fmt = _format_id(input_format)
         self.n_channels = int(n_channels)
-        self.interpolation = 1
+        self.interpolation = 1 if _interpolation is None else int(_interpolation)
         self.decimation = int(decimation)
-        self._stream = None
         taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        h = _lib._h()
-        _lib.check(_lib.lib().rfa_pfb_create(device, self.fmt, self.n_channels, self.decimation,
-                                             taps.ctypes.data_as(_lib._fp), taps.size, ctypes.byref(h)),
-                   "rfa_pfb_create")
-        self._h = h
+        if _interpolation is None:
+            self._create("rfa_pfb_create", device, self.fmt, self.n_channels, self.decimation,
+                         taps.ctypes.data_as(_lib._fp), taps.size)
+        else:               # Channelizer.rational, L = 1 included
+            self._create("rfa_pfb_create_rational", device, self.fmt, self.n_channels, self.interpolation,
+                         self.decimation, taps.ctypes.data_as(_lib._fp), taps.size)
         self._n_selected = self.n_channels
 
     @classmethod
@@ -1045,23 +911,7 @@ class Channelizer:
         n has phase (n * D) mod L and newest sample floor(n * D / L); after c samples ceil(c * L / D)
         outputs exist.  L = 1 keeps that convention (m_n = n * D), which is not the plain
         constructor's n * D + D - 1."""
-        if input_format not in FORMATS:
-            raise ValueError(f"input_format must be one of {sorted(FORMATS)}")
-        self = cls.__new__(cls)
-        self._h = None
-        self.fmt = FORMATS[input_format]
-        self.n_channels = int(n_channels)
-        self.interpolation = int(interpolation)
-        self.decimation = int(decimation)
-        self._stream = None
-        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-        h = _lib._h()
-        _lib.check(_lib.lib().rfa_pfb_create_rational(device, self.fmt, self.n_channels, self.interpolation,
-                                                      self.decimation, taps.ctypes.data_as(_lib._fp), taps.size,
-                                                      ctypes.byref(h)), "rfa_pfb_create_rational")
-        self._h = h
-        self._n_selected = self.n_channels
-        return self
+        return cls(input_format, n_channels, decimation, taps, device, _interpolation=int(interpolation))
 
     @staticmethod
     def raster_ratio(sample_rate: int, spacing_hz: int, output_rate: int) -> tuple[int, int, int]:
@@ -1118,44 +968,20 @@ class Channelizer:
             raise ValueError("the low-pass design rejected the raster")
         return cls(input_format, sample_rate // spacing_hz, sample_rate // output_rate, taps, device)
 
-    # -- lifetime
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            _lib.lib().rfa_pfb_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-    def _check(self, status: int, where: str) -> None:
-        if status != _lib.RFA_OK:
-            detail = (_lib.lib().rfa_pfb_last_error(self._h) or b"").decode()
-            raise _lib.RfaError(status, where, detail)
-
     # -- configuration
     def set_channels(self, channels=None) -> None:
         """Slot j is channel ``channels[j]`` (any order, repeats allowed); None or empty: all
         channels in natural order.  An invalid list raises and leaves the selection as it was."""
         ch = [int(c) for c in channels] if channels is not None else []
         arr = (ctypes.c_int32 * max(len(ch), 1))(*ch)
-        self._check(_lib.lib().rfa_pfb_set_channels(self._h, arr if ch else None, len(ch)), "rfa_pfb_set_channels")
+        self._call("set_channels", arr if ch else None, len(ch))
         self._n_selected = len(ch) or self.n_channels
 
     @property
     def channels(self) -> list[int]:
         n = ctypes.c_int32(0)
         out = (ctypes.c_int32 * self.n_channels)()
-        self._check(_lib.lib().rfa_pfb_get_channels(self._h, out, self.n_channels, ctypes.byref(n)),
-                    "rfa_pfb_get_channels")
+        self._call("get_channels", out, self.n_channels, ctypes.byref(n))
         return list(out[:n.value])
 
     def channel_of(self, frequency: int, channel_frequency: int, sample_rate: int) -> int:
@@ -1171,47 +997,38 @@ class Channelizer:
         """{"n_channels", "decimation", "num_taps", "radices"}: the DFT's radices in stage order."""
         v = [ctypes.c_int32(0) for _ in range(4)]
         rad = (ctypes.c_int32 * 16)()
-        self._check(_lib.lib().rfa_pfb_get_plan(self._h, ctypes.byref(v[0]), ctypes.byref(v[1]), ctypes.byref(v[2]),
-                                                rad, 16, ctypes.byref(v[3])), "rfa_pfb_get_plan")
+        self._call("get_plan", ctypes.byref(v[0]), ctypes.byref(v[1]), ctypes.byref(v[2]), rad, 16, ctypes.byref(v[3]))
         return {"n_channels": v[0].value, "decimation": v[1].value, "num_taps": v[2].value,
                 "radices": list(rad[:v[3].value])}
 
     @property
     def taps(self) -> np.ndarray:
-        n = ctypes.c_int32(0)
-        L = _lib.lib()
-        self._check(L.rfa_pfb_get_taps(self._h, None, 0, ctypes.byref(n)), "rfa_pfb_get_taps")
-        out = np.empty(n.value, np.float32)
-        self._check(L.rfa_pfb_get_taps(self._h, out.ctypes.data_as(_lib._fp), out.size, ctypes.byref(n)),
-                    "rfa_pfb_get_taps")
-        return out
+        return self._query_floats("get_taps", 1, 1)[0][0]
 
     @property
     def ratio(self) -> tuple[int, int, int]:
         """(interpolation, decimation, taps per output) as ``rfa_pfb_get_ratio`` reports them:
         (1, D, T) on an integer handle, (L, D, ceil(T / L)) on a rational one."""
         v = [ctypes.c_int32(0) for _ in range(3)]
-        self._check(_lib.lib().rfa_pfb_get_ratio(self._h, *[ctypes.byref(x) for x in v]), "rfa_pfb_get_ratio")
+        self._call("get_ratio", *[ctypes.byref(x) for x in v])
         return v[0].value, v[1].value, v[2].value
 
     def max_outputs(self, n_samples: int) -> int:
         """The exact output count per channel of the next call of ``n_samples``."""
         n = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_pfb_max_outputs(self._h, n_samples, ctypes.byref(n)), "rfa_pfb_max_outputs")
+        self._call("max_outputs", n_samples, ctypes.byref(n))
         return n.value
 
     # -- processing
     def process(self, data) -> list[np.ndarray]:
         """Host bytes / numpy in -> one complex64 array per selected channel."""
-        buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview))
-                                   else np.asarray(data).view(np.uint8).reshape(-1))
+        buf = _raw_bytes(data)
         n = buf.size // BYTES_PER_SAMPLE[self.fmt]
         cap = max(self.max_outputs(n), 1)
         re = np.empty((self._n_selected, cap), np.float32)
         im = np.empty((self._n_selected, cap), np.float32)
         got = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_pfb_process_host(self._h, buf.ctypes.data, n, re.ctypes.data, im.ctypes.data, cap,
-                                                    ctypes.byref(got)), "rfa_pfb_process_host")
+        self._call("process_host", buf.ctypes.data, n, re.ctypes.data, im.ctypes.data, cap, ctypes.byref(got))
         out = np.empty((self._n_selected, got.value), np.complex64)
         out.real, out.imag = re[:, :got.value], im[:, :got.value]
         return list(out)
@@ -1220,18 +1037,13 @@ class Channelizer:
         """Device pointers, outputs [selected][channel_stride] floats; asynchronous on the handle's
         stream; returns the output count per channel."""
         got = ctypes.c_size_t(0)
-        self._check(_lib.lib().rfa_pfb_process(self._h, in_ptr, n_samples, re_ptr, im_ptr, channel_stride,
-                                               ctypes.byref(got)), "rfa_pfb_process")
+        self._call("process", in_ptr, n_samples, re_ptr, im_ptr, channel_stride, ctypes.byref(got))
         return got.value
 
     def process_tensor(self, raw, out_re, out_im) -> int:
         """torch.cuda tensors: raw bytes (contiguous) -> float32 outputs of shape [selected, stride],
         on torch's current stream (see ``FrontEnd.process_tensor``)."""
-        import torch
-
-        cur = torch.cuda.current_stream(raw.device).cuda_stream
-        if cur != self._stream:
-            self.set_stream(cur)
+        self._follow_torch_stream(raw)
         n = raw.numel() * raw.element_size() // BYTES_PER_SAMPLE[self.fmt]
         if out_re.shape != out_im.shape or out_re.dim() != 2 or out_re.shape[0] != self._n_selected:
             raise ValueError(f"out_re and out_im must both have shape [{self._n_selected}, stride]")
@@ -1241,24 +1053,10 @@ class Channelizer:
 
     def reset(self) -> None:
         """History zeroed, sample count 0."""
-        self._check(_lib.lib().rfa_pfb_reset(self._h), "rfa_pfb_reset")
-
-    def set_stream(self, stream_ptr: int | None) -> None:
-        """Enqueue on exactly this hipStream_t (None: the handle's own stream)."""
-        self._check(_lib.lib().rfa_pfb_set_stream(self._h, stream_ptr or None), "rfa_pfb_set_stream")
-        self._stream = stream_ptr or None
-
-    def synchronize(self) -> None:
-        self._check(_lib.lib().rfa_pfb_synchronize(self._h), "rfa_pfb_synchronize")
-
-    @property
-    def stream(self) -> int:
-        s = _lib._vp()
-        self._check(_lib.lib().rfa_pfb_get_stream(self._h, ctypes.byref(s)), "rfa_pfb_get_stream")
-        return s.value or 0
+        self._call("reset")
 
 
-class RasterReceiverBank:
+class RasterReceiverBank(_BankChain):
     """Raw IQ bytes -> one audio stream per raster channel: a ``Channelizer.for_raster`` at the
     modes' common quadrature rate feeding a ``DemodulatorBank``, device to device on one stream,
     2 + 4 launches per packet whatever the channel count.  Slot k demodulates raster channel
@@ -1268,114 +1066,28 @@ class RasterReceiverBank:
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0,
                  resample: bool = False):
-        import torch
-
-        modes = list(modes)
-        if not modes:
-            raise ValueError("at least one mode")
-        rates = {mode_info(m)[0] for m in modes}
-        if len(rates) != 1:
-            raise ValueError(f"the modes' quadrature rates differ: {sorted(rates)}")
+        modes, rate = _common_rate(modes)
         channels = list(range(len(modes))) if channels is None else [int(c) for c in channels]
         if len(channels) != len(modes):
             raise ValueError(f"{len(modes)} channels expected, got {len(channels)}")
-        self._torch = torch
-        self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
-        self._tdev = torch.device("cuda", device)
-        self.quadrature_rate = rates.pop()
-        self.demods, self.front = None, None
-        self._n_channels = len(modes)
-        self._raw = self._re = self._im = self._audio = None
-        try:
-            self.demods = DemodulatorBank(modes, device)
-            self._resample = bool(resample)
-            make = Channelizer.for_raster_resampled if self._resample else Channelizer.for_raster
-            self.front = make(input_format, self.sample_rate, spacing_hz, self.quadrature_rate, device)
-            self.front.set_channels(channels)
-            self.set_stream(None)
-        except Exception:
-            self.close()
-            raise
+        self._resample = bool(resample)
+        super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, channels)
 
-    @property
-    def n_channels(self) -> int:
-        return self._n_channels
+    def _make_front(self, spacing_hz: int, channels):
+        make = Channelizer.for_raster_resampled if self._resample else Channelizer.for_raster
+        front = make(self.input_format, self.sample_rate, spacing_hz, self.quadrature_rate, self.device)
+        try:
+            front.set_channels(channels)
+        except Exception:
+            front.close()
+            raise
+        return front
+
+    def _capacity(self, n: int) -> int:
+        if self._resample:                            # ceil(c1 L / D) - ceil(c0 L / D) <= ceil(n L / D)
+            return -(-n * self.front.interpolation // self.front.decimation) + 1
+        return n // self.front.decimation + 1         # an upper bound of any call of n samples
 
     @property
     def channels(self) -> list[int]:
         return self.front.channels
-
-    def mode(self, k: int) -> int:
-        return self.demods.mode(k)
-
-    def set_mode(self, k: int, mode) -> None:
-        """Slot k's DemodulationMode; only to a mode of the bank's quadrature rate."""
-        if mode_info(mode)[0] != self.quadrature_rate:
-            raise ValueError(f"mode {mode!r} has quadrature rate {mode_info(mode)[0]}, the bank runs at "
-                             f"{self.quadrature_rate}")
-        self.demods.set_mode(k, mode)
-
-    def set_stream(self, stream_ptr: int | None) -> None:
-        """Enqueue every stage on exactly this hipStream_t (None: the demodulator bank's own)."""
-        self.demods.set_stream(stream_ptr)
-        self.front.set_stream(self.demods.stream)
-
-    def synchronize(self) -> None:
-        self.demods.synchronize()
-
-    def _buffers(self, nbytes: int, n: int) -> int:
-        torch = self._torch
-        if self._raw is None or self._raw.numel() < nbytes:
-            self._raw = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self._tdev)
-        if self._resample:                            # ceil(c1 L / D) - ceil(c0 L / D) <= ceil(n L / D)
-            cap = -(-n * self.front.interpolation // self.front.decimation) + 1
-        else:
-            cap = n // self.front.decimation + 1      # an upper bound of any call of n samples
-        if self._re is None or self._re.shape[1] < cap:
-            shape = (self.n_channels, cap)
-            self._re = torch.empty(shape, dtype=torch.float32, device=self._tdev)
-            self._im = torch.empty(shape, dtype=torch.float32, device=self._tdev)
-            self._audio = torch.empty(shape, dtype=torch.float32, device=self._tdev)
-        return self._re.shape[1]
-
-    def process_device(self, raw_ptr: int, n_samples: int) -> list[int]:
-        """Raw samples at a device address -> audio left in the rows of ``self.audio_tensor``;
-        asynchronous on the bank's stream; returns every slot's audio sample count."""
-        cap = self._buffers(0, n_samples)
-        nq = self.front.process_device(raw_ptr, n_samples, self._re.data_ptr(), self._im.data_ptr(), cap)
-        return self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq, self._audio.data_ptr(),
-                                          cap)
-
-    @property
-    def audio_tensor(self):
-        return self._audio
-
-    def process(self, raw_bytes) -> list[np.ndarray]:
-        """One raw input packet (host bytes) -> K float32 audio arrays."""
-        torch = self._torch
-        buf = np.ascontiguousarray(np.frombuffer(raw_bytes, np.uint8)
-                                   if isinstance(raw_bytes, (bytes, bytearray, memoryview))
-                                   else np.asarray(raw_bytes).view(np.uint8).reshape(-1))
-        n = buf.size // BYTES_PER_SAMPLE[self.front.fmt]
-        self._buffers(buf.size, n)
-        self.synchronize()                            # the staging buffer's previous use is over
-        self._raw[:buf.size].copy_(torch.from_numpy(buf.copy()))
-        torch.cuda.synchronize(self._tdev)
-        got = self.process_device(self._raw.data_ptr(), n)
-        self.synchronize()
-        audio = self._audio.cpu().numpy()
-        return [audio[k, :g].copy() for k, g in enumerate(got)]
-
-    def close(self) -> None:
-        if self.front is not None:
-            self.front.close()
-            self.front = None
-        if self.demods is not None:
-            self.demods.close()
-            self.demods = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
