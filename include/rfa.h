@@ -590,7 +590,9 @@ RFA_API int rfa_ddc_tile_plan(int32_t taps_per_output, int32_t interpolation, in
  * Polyphase channelizer: all n_channels = M channels of the
  * uniform raster k * Fs / M out of one raw IQ stream per call, for a cost that
  * does not grow with the channel count.  For channels on a raster it replaces
- * the front-end channel bank above; arbitrary frequencies stay with the bank.
+ * the front-end channel bank above; a tuning (rfa_pfb_set_tuning, below) moves a
+ * slot up to half a spacing off its raster centre, so any frequency list runs here
+ * too.  Only a bit-for-bit match with the app's own Resampler stays with the bank.
  * With x[j] the converted input (s8: b/128, u8: (b-127.4f)/128, s16: s/32768,
  * float I,Q as it is; j counts samples since creation or reset, x[j] = 0 for
  * j < 0), real prototype taps h[0..T-1] and integer decimation D, output n is
@@ -634,7 +636,9 @@ RFA_API int rfa_pfb_get_taps(const rfa_pfb *p, float *taps, size_t capacity, int
  * order, repeats allowed, 1 <= count <= n_channels; count 0 or a NULL list
  * selects all channels in natural order.  Uploaded between calls (drains the
  * stream).  An invalid list is RFA_ERR_INVALID and leaves the selection as it
- * was.  The selection changes which rows are written, never their values. */
+ * was.  The selection changes which rows are written, never their values.
+ * A successful call also removes any tuning (rfa_pfb_set_tuning): the slots it
+ * creates are untuned. */
 RFA_API int rfa_pfb_set_channels(rfa_pfb *p, const int32_t *channels, int32_t count);
 RFA_API int rfa_pfb_get_channels(const rfa_pfb *p, int32_t *channels, size_t capacity, int32_t *count);
 /* The exact output count per channel of the next call of n_samples:
@@ -707,6 +711,56 @@ RFA_API int rfa_pfb_get_ratio(const rfa_pfb *p, int32_t *interpolation, int32_t 
  * L > D, gcd != 1), a null n, or consumed + n_samples >= 2^53. */
 RFA_API int rfa_pfb_rational_outputs(int32_t interpolation, int32_t decimation, uint64_t consumed, size_t n_samples,
                                      size_t *n);
+
+/* Fine tuning: receivers at any frequency, not only on the
+ * raster.  A handle of either create entry may carry a tuning: a denominator Q
+ * and one integer step m_j per output slot j (a slot is an entry of the selection
+ * set by rfa_pfb_set_channels).  With y_k[n] the output defined above and n the
+ * absolute output index since creation or rfa_pfb_reset (a 64-bit count), slot j
+ * writes
+ *   i      = (n * m_j) mod Q                 mathematical mod, 0 <= i < Q, exact in integers
+ *   (c, s) = W[i]                            W[i] = (float cos(2 pi i / Q), float sin(2 pi i / Q))
+ *   z_re   = y_re * c + y_im * s             fp32, both products and the sum rounded separately
+ *   z_im   = y_im * c - y_re * s
+ * that is z = y * exp(-j 2 pi m_j n / Q): a signal m_j * Fout / Q Hz above the
+ * raster centre of channels[j] lands at DC (Fout: the output rate).  The output
+ * rate is several times the raster spacing, so a prototype with a pass band of
+ * half a spacing plus the channel's width lets any frequency through its nearest
+ * raster channel, and the demodulator's own filter selects the channel.
+ * A slot with m_j == 0 is written untouched, with no multiply: NaN, inf and every
+ * bit of it are those of an untuned handle.  The phase is a function of n alone:
+ * it does not depend on how the stream is cut into calls and there is no per-slot
+ * state, so nothing drifts; rfa_pfb_reset restarts n at 0 and keeps the tuning.
+ * W is built once on the host in double, the angle first reduced by symmetry to
+ * the first octant, each value rounded to float once: W[0] = (1, 0) exactly and,
+ * where 4 divides Q, W[Q/4] = (0, 1), W[Q/2] = (-1, 0), W[3Q/4] = (0, -1) exactly.
+ * One table of Q entries (8 Q bytes) is shared by all slots and uploaded with the
+ * tuning. */
+#define RFA_PFB_TUNE_MAX_STEPS (1 << 20)   /* Q at most: 1 Hz steps at up to 1.048 MHz output rate */
+
+/* 1 <= q <= RFA_PFB_TUNE_MAX_STEPS, count equal to the number of currently
+ * selected slots, -q < steps[j] < q.  q == 0 or steps == NULL removes the tuning
+ * (with q == 0 and steps given, count is still checked).  An invalid request is
+ * RFA_ERR_INVALID and leaves the previous tuning as it was.  Uploaded between
+ * calls (drains the stream; may allocate) and in force from the next output.  A
+ * call of rfa_pfb_process on a tuned handle is still two launches -- the rotation
+ * is part of the store of the fold + DFT kernel -- and allocates nothing; a
+ * handle without a tuning launches the kernels it launched before this entry
+ * existed.  rfa_pfb_set_channels removes the tuning. */
+RFA_API int rfa_pfb_set_tuning(rfa_pfb *p, int32_t q, const int32_t *steps, int32_t count);
+/* The denominator and the steps as given; *q = 0 and *count = 0 when there is no
+ * tuning.  RFA_ERR_SIZE where steps is given and capacity is smaller than the
+ * count.  Any output pointer may be NULL. */
+RFA_API int rfa_pfb_get_tuning(const rfa_pfb *p, int32_t *q, int32_t *steps, size_t capacity, int32_t *count);
+/* Host only, no handle and no device needed: *i = (n * step) mod q for n < 2^53,
+ * by the very function the kernel calls (a multiply-high reduction, no division).
+ * RFA_ERR_INVALID for q outside 1 .. RFA_PFB_TUNE_MAX_STEPS, |step| >= q,
+ * n >= 2^53 or a null i. */
+RFA_API int rfa_pfb_tuning_index(int32_t q, int32_t step, uint64_t n, int32_t *i);
+/* Host only: the table W a handle uploads for q, cos_t[i] and sin_t[i] for
+ * 0 <= i < q.  RFA_ERR_INVALID for q out of range or a null array, RFA_ERR_SIZE
+ * for capacity < q. */
+RFA_API int rfa_pfb_tuning_table(int32_t q, float *cos_t, float *sin_t, size_t capacity);
 
 /* ------------------------------------------------------------------------
  * Demodulator: quadrature-rate IQ (what rfa_ddc_process writes, planar float

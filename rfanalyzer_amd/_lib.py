@@ -26,6 +26,7 @@ RFA_ERR_HIP = -6
 RFA_ERR_STATE = -7
 
 RFA_PFB_MAX_INTERPOLATION = 64      # include/rfa.h
+RFA_PFB_TUNE_MAX_STEPS = 1 << 20    # include/rfa.h
 
 WINDOWS = {"blackman": 0, "hann": 1, "none": 2}
 FORMATS = {"s8": 0, "u8": 1, "s16": 2, "f32": 3, "f32p": 4}
@@ -226,6 +227,12 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_pfb_get_ratio": (ctypes.c_int, [_h] + [ctypes.POINTER(ctypes.c_int32)] * 3),
         "rfa_pfb_rational_outputs": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t,
                                                     ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_pfb_set_tuning": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
+        "rfa_pfb_get_tuning": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_pfb_tuning_index": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                                ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_pfb_tuning_table": (ctypes.c_int, [ctypes.c_int32, _fp, _fp, ctypes.c_size_t]),
         # demodulator (rfanalyzer_amd/demod.py Demodulator, Receiver)
         "rfa_demod_mode_info": (ctypes.c_int, [ctypes.c_int] + [ctypes.POINTER(ctypes.c_int32)] * 4),
         "rfa_bandpass_taps": (ctypes.c_int, [ctypes.c_float] * 6 + [_fp, _fp, ctypes.c_size_t,

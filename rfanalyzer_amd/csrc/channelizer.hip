@@ -32,6 +32,11 @@
 // rfa_pfb_create_rational runs the same raster at L / D times the input rate:
 // pfb_rational_kernel below folds with one of L sub-filters per output and shares
 // everything else; pfb_kernel is the code the integer entry launches, unchanged.
+//
+// rfa_pfb_set_tuning moves a slot off its raster centre: the TUNED instantiations
+// of both kernels are the same tiles with a rotation by a table entry compiled
+// into the store (pfb_store), so a tuned call is still two launches and a handle
+// without a tuning launches the code it always did.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +45,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rfa.h"
@@ -76,6 +82,42 @@ struct PfbLaunch {
     long long stride;              // floats between two slots' rows
     float *out_re, *out_im;
 };
+
+// ---------------------------------------------------------------- tuning (rfa_pfb_set_tuning)
+//
+// Slot j of a tuned handle writes y * exp(-j 2 pi m_j n / Q) with n the absolute output index:
+// the table entry (n * m_j) mod Q.  The reduction is the one below on the host and on the
+// device: x mod q from the high half of x * mu, mu = floor((2^64 - 1) / q).  With
+// 2^64 / q - 1 <= mu <= 2^64 / q the estimate floor(x mu / 2^64) is floor(x / q) or one less for
+// every x < 2^64, so one conditional subtraction ends in [0, q): no division, and no x for
+// which the index leaves the table.
+struct PfbTune {
+    const float2 *w;               // W[i] = (cos, sin)(2 pi i / q), q entries
+    const int *step;               // slot -> m_j, -q < m_j < q
+    unsigned q;
+    unsigned long long mu;         // floor((2^64 - 1) / q)
+};
+
+__host__ __device__ inline unsigned long long pfb_tune_mu(unsigned q) { return ~0ull / q; }
+
+__host__ __device__ inline unsigned pfb_tune_mod(unsigned long long x, unsigned q, unsigned long long mu) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned long long est = __umul64hi(x, mu);
+#else
+    const unsigned long long est = (unsigned long long)(((unsigned __int128)x * mu) >> 64);
+#endif
+    unsigned long long r = x - est * q;
+    if (r >= q) r -= q;
+    return (unsigned)r;
+}
+
+// (n * m) mod q, mathematical mod, for -q < m < q <= RFA_PFB_TUNE_MAX_STEPS: n is reduced first,
+// so the product stays below 2^40.
+__host__ __device__ inline unsigned pfb_tune_index(unsigned q, unsigned long long mu, int m, unsigned long long n) {
+    const unsigned r = pfb_tune_mod(n, q, mu);
+    const unsigned mm = m < 0 ? (unsigned)(m + (int)q) : (unsigned)m;
+    return pfb_tune_mod((unsigned long long)r * mm, q, mu);
+}
 
 // One complex input sample, converted by the code the front end converts with before it
 // mixes (raw_to_iq of stage_common.h); g is call-relative, negative values index the history.
@@ -152,8 +194,49 @@ __device__ __forceinline__ void pfb_stage(const PfbLaunch &a, const float2 *src,
     }
 }
 
-template <int FMT>
-__global__ __launch_bounds__(kPfbThreads) void pfb_kernel(PfbLaunch a) {
+// The selected channels of a tile's finished DFT rows, time along the lanes.  TUNED: slot j is
+// rotated by W[(n * m_j) mod q] on its way out (include/rfa.h, rfa_pfb_set_tuning); a slot with
+// m_j == 0 is stored as it is, without a multiply.
+template <bool TUNED>
+__device__ __forceinline__ void pfb_store(const PfbLaunch &a, const PfbTune &t, const float2 *src, long long m0,
+                                          int nloc) {
+    const int sh = 31 - __clz(a.NT);
+    for (int item = threadIdx.x; item < a.K * a.NT; item += kPfbThreads) {
+        const int slot = item >> sh, nl = item & (a.NT - 1);
+        if (nl < nloc) {
+            float2 v = src[nl * a.Mp + a.chan[slot]];
+            const long long o = (long long)slot * a.stride + m0 + nl;
+            if constexpr (TUNED) {
+                const int m = t.step[slot];
+                if (m != 0) {
+                    const float2 w = t.w[pfb_tune_index(t.q, t.mu, m, (unsigned long long)(a.n0 + m0 + nl))];
+                    v = float2{v.x * w.x + v.y * w.y, v.y * w.x - v.x * w.y};
+                }
+            }
+            a.out_re[o] = v.x;
+            a.out_im[o] = v.y;
+        }
+    }
+}
+
+// The kernel is instantiated per launch record.  Rec = PfbLaunch is the kernel of a handle without a
+// tuning: no PfbTune reaches it and its code is what it was before tunings existed.
+// Rec = PfbTunedLaunch carries the tuning behind the same record and compiles the rotation into the
+// store.
+struct PfbTunedLaunch {
+    PfbLaunch a;
+    PfbTune t;
+};
+__device__ __forceinline__ const PfbLaunch &pfb_record(const PfbLaunch &r) { return r; }
+__device__ __forceinline__ const PfbLaunch &pfb_record(const PfbTunedLaunch &r) { return r.a; }
+__device__ __forceinline__ PfbTune pfb_tuning(const PfbLaunch &) { return PfbTune{}; }
+__device__ __forceinline__ PfbTune pfb_tuning(const PfbTunedLaunch &r) { return r.t; }
+
+template <int FMT, class Rec = PfbLaunch>
+__global__ __launch_bounds__(kPfbThreads) void pfb_kernel(Rec rec) {
+    constexpr bool TUNED = !std::is_same_v<Rec, PfbLaunch>;
+    const PfbLaunch &a = pfb_record(rec);
+    const PfbTune t = pfb_tuning(rec);
     extern __shared__ __attribute__((aligned(16))) float2 pfb_lds[];
     // [staged run | taps] (a.stage points, absent where the fold reads global memory) | DFT rows x 2
     float2 *src = pfb_lds + a.stage, *dst = src + a.NT * a.Mp;
@@ -213,17 +296,7 @@ __global__ __launch_bounds__(kPfbThreads) void pfb_kernel(PfbLaunch a) {
         dst = sw;
         p *= R;
     }
-    // selected channels, time along the lanes
-    const int sh = 31 - __clz(a.NT);
-    for (int item = tid; item < a.K * a.NT; item += kPfbThreads) {
-        const int slot = item >> sh, nl = item & (a.NT - 1);
-        if (nl < nloc) {
-            const float2 v = src[nl * a.Mp + a.chan[slot]];
-            const long long o = (long long)slot * a.stride + m0 + nl;
-            a.out_re[o] = v.x;
-            a.out_im[o] = v.y;
-        }
-    }
+    pfb_store<TUNED>(a, t, src, m0, nloc);
 }
 
 // new_hist[t] = sample S - (T-1) + t of the extended sequence [hist | raw].
@@ -260,8 +333,9 @@ struct PfbRatLaunch {
 };
 
 // The stage loop and the store of pfb_kernel, which stays as it is.
-__device__ __forceinline__ void pfb_dft_store(const PfbLaunch &a, float2 *src, float2 *dst, long long m0, int nloc) {
-    const int tid = threadIdx.x;
+template <bool TUNED>
+__device__ __forceinline__ void pfb_dft_store(const PfbLaunch &a, const PfbTune &t, float2 *src, float2 *dst,
+                                              long long m0, int nloc) {
     int p = 1;
     for (int s = 0; s < a.nstages; s++) {
         const int R = a.radix[s];
@@ -276,20 +350,23 @@ __device__ __forceinline__ void pfb_dft_store(const PfbLaunch &a, float2 *src, f
         dst = sw;
         p *= R;
     }
-    const int sh = 31 - __clz(a.NT);
-    for (int item = tid; item < a.K * a.NT; item += kPfbThreads) {
-        const int slot = item >> sh, nl = item & (a.NT - 1);
-        if (nl < nloc) {
-            const float2 v = src[nl * a.Mp + a.chan[slot]];
-            const long long o = (long long)slot * a.stride + m0 + nl;
-            a.out_re[o] = v.x;
-            a.out_im[o] = v.y;
-        }
-    }
+    pfb_store<TUNED>(a, t, src, m0, nloc);
 }
 
-template <int FMT>
-__global__ __launch_bounds__(kPfbThreads) void pfb_rational_kernel(PfbRatLaunch b) {
+struct PfbRatTunedLaunch {
+    PfbRatLaunch b;
+    PfbTune t;
+};
+__device__ __forceinline__ const PfbRatLaunch &pfb_record(const PfbRatLaunch &r) { return r; }
+__device__ __forceinline__ const PfbRatLaunch &pfb_record(const PfbRatTunedLaunch &r) { return r.b; }
+__device__ __forceinline__ PfbTune pfb_tuning(const PfbRatLaunch &) { return PfbTune{}; }
+__device__ __forceinline__ PfbTune pfb_tuning(const PfbRatTunedLaunch &r) { return r.t; }
+
+template <int FMT, class Rec = PfbRatLaunch>
+__global__ __launch_bounds__(kPfbThreads) void pfb_rational_kernel(Rec rec) {
+    constexpr bool TUNED = !std::is_same_v<Rec, PfbRatLaunch>;
+    const PfbRatLaunch &b = pfb_record(rec);
+    const PfbTune t = pfb_tuning(rec);
     extern __shared__ __attribute__((aligned(16))) float2 pfb_lds[];
     __shared__ int t_dm[kPfbMaxTimes], t_ph[kPfbMaxTimes], t_mm[kPfbMaxTimes];   // m_n - m_first, p_n, m_n mod M
     const PfbLaunch &a = b.a;
@@ -350,12 +427,12 @@ __global__ __launch_bounds__(kPfbThreads) void pfb_rational_kernel(PfbRatLaunch 
         src[nl * a.Mp + r] = acc;
     }
     __syncthreads();
-    pfb_dft_store(a, src, dst, m0, nloc);
+    pfb_dft_store<TUNED>(a, t, src, dst, m0, nloc);
 }
 
 int pfb_lds_bytes(const PfbLaunch &a) { return (a.stage + 2 * a.NT * a.Mp) * (int)sizeof(float2); }
 
-// kernel: pfb_kernel<FMT> (its record is a PfbLaunch) or pfb_rational_kernel<FMT> (a PfbRatLaunch)
+// kernel: pfb_kernel<FMT, Rec> or pfb_rational_kernel<FMT, Rec>
 template <class Rec>
 hipError_t pfb_prepare(void (*kernel)(Rec)) {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -456,6 +533,23 @@ long long pfb_gcd(long long a, long long b) {
 // Outputs due once c samples are consumed: ceil(c * L / D); c < 2^53 and L <= 64 keep the product in range.
 long long pfb_rational_count(long long c, int L, int D) { return (c * L + D - 1) / D; }
 
+// W[i] = (cos, sin)(2 pi i / q) of a tuning, in double and rounded to float once.  The angle is
+// reduced to the first octant in integers (in eighths of a table step, so the octant's edges are
+// exact), which makes the four axis points exact and the table symmetric.
+float2 pfb_tune_entry(long long i, long long q) {
+    long long e = 8 * i;                                         // angle = 2 pi e / (8 q), 0 <= e < 8 q
+    bool neg_s = false, neg_c = false, swap = false;
+    if (e > 4 * q) e = 8 * q - e, neg_s = true;                  // [0, pi]
+    if (e > 2 * q) e = 4 * q - e, neg_c = true;                  // [0, pi / 2]
+    if (e > q) e = 2 * q - e, swap = true;                       // [0, pi / 4]
+    const double ang = 2.0 * M_PI * (double)e / (double)(8 * q);
+    double c = std::cos(ang), s = std::sin(ang);
+    if (swap) std::swap(c, s);
+    return float2{(float)(neg_c ? -c : c), (float)(neg_s ? -s : s)};
+}
+
+bool pfb_tune_q_valid(int32_t q) { return q >= 1 && q <= RFA_PFB_TUNE_MAX_STEPS; }
+
 }  // namespace
 
 struct rfa_pfb : StageCore {
@@ -474,6 +568,13 @@ struct rfa_pfb : StageCore {
     int *d_chan = nullptr;              // M entries
     float *d_hist[2] = {nullptr, nullptr};
     int cur = 0;
+    // tuning (rfa_pfb_set_tuning); tune_q == 0: none, and nothing below is read
+    int32_t tune_q = 0;
+    std::vector<int32_t> tune_steps;    // slot -> m_j as given
+    float2 *d_tune_w = nullptr;         // tune_w_cap entries
+    size_t tune_w_cap = 0;
+    int *d_tune_step = nullptr;         // M entries
+    bool tuned_prepared = false;        // the tuned kernels' LDS attribute is set
     // staging for the _host entry point
     void *d_in = nullptr;
     size_t d_in_cap = 0;
@@ -605,7 +706,7 @@ int rfa_pfb_destroy(rfa_pfb *p) {
     if (!p) return RFA_ERR_INVALID;
     stage_close_stream(p);
     for (void *q : {(void *)p->d_taps, (void *)p->d_tw, (void *)p->d_chan, (void *)p->d_hist[0], (void *)p->d_hist[1],
-                    p->d_in, (void *)p->d_out})
+                    p->d_in, (void *)p->d_out, (void *)p->d_tune_w, (void *)p->d_tune_step})
         if (q) hipFree(q);
     delete p;
     return RFA_OK;
@@ -654,6 +755,90 @@ int rfa_pfb_set_channels(rfa_pfb *p, const int32_t *channels, int32_t count) {
     STAGE_HIP(p, hipMemcpyAsync(p->d_chan, ch.data(), ch.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
     STAGE_HIP(p, hipStreamSynchronize(p->stream));
     p->channels = std::move(ch);
+    p->tune_q = 0;                                     // the new slots are untuned
+    p->tune_steps.clear();
+    return RFA_OK;
+}
+
+int rfa_pfb_set_tuning(rfa_pfb *p, int32_t q, const int32_t *steps, int32_t count) {
+    if (!p) return RFA_ERR_INVALID;
+    if (q == 0 || !steps) {
+        if (q != 0 && !pfb_tune_q_valid(q)) return stage_fail(p, RFA_ERR_INVALID, "tuning denominator outside 1 .. RFA_PFB_TUNE_MAX_STEPS");
+        if (steps && count != (int32_t)p->channels.size())
+            return stage_fail(p, RFA_ERR_INVALID, "tuning count differs from the selection");
+        p->tune_q = 0;                                 // the next call launches the untuned kernels again
+        p->tune_steps.clear();
+        return RFA_OK;
+    }
+    if (!pfb_tune_q_valid(q)) return stage_fail(p, RFA_ERR_INVALID, "tuning denominator outside 1 .. RFA_PFB_TUNE_MAX_STEPS");
+    if (count != (int32_t)p->channels.size())
+        return stage_fail(p, RFA_ERR_INVALID, "tuning count differs from the selection");
+    for (int32_t j = 0; j < count; j++)
+        if (steps[j] <= -q || steps[j] >= q) return stage_fail(p, RFA_ERR_INVALID, "tuning step outside -q < m < q");
+    STAGE_HIP(p, hipSetDevice(p->device));
+    if (!p->tuned_prepared) {
+        for (int fmt : {RFA_IN_S8, RFA_IN_U8, RFA_IN_S16LE, RFA_IN_F32_INTERLEAVED}) {
+            STAGE_HIP(p, stage_dispatch_format(
+                             fmt, [](auto f) { return pfb_prepare(pfb_kernel<decltype(f)::value, PfbTunedLaunch>); }));
+            STAGE_HIP(p, stage_dispatch_format(
+                             fmt, [](auto f) { return pfb_prepare(pfb_rational_kernel<decltype(f)::value, PfbRatTunedLaunch>); }));
+        }
+        p->tuned_prepared = true;
+    }
+    // a table or step list an enqueued call still reads is neither freed nor overwritten
+    STAGE_HIP(p, hipStreamSynchronize(p->stream));
+    if (!p->d_tune_step && hipMalloc(&p->d_tune_step, (size_t)p->M * sizeof(int)) != hipSuccess)
+        return stage_fail(p, RFA_ERR_NOMEM, "hipMalloc tuning steps");
+    const bool new_table = q != p->tune_q || !p->d_tune_w;
+    if ((size_t)q > p->tune_w_cap) {
+        float2 *w = nullptr;
+        if (hipMalloc(&w, (size_t)q * sizeof(float2)) != hipSuccess)
+            return stage_fail(p, RFA_ERR_NOMEM, "hipMalloc tuning table");
+        if (p->d_tune_w) hipFree(p->d_tune_w);
+        p->d_tune_w = w;
+        p->tune_w_cap = (size_t)q;
+        p->tune_q = 0;                                 // the old table is gone: no tuning until the new one is up
+        p->tune_steps.clear();
+    }
+    if (new_table) {
+        std::vector<float2> w((size_t)q);
+        for (int32_t i = 0; i < q; i++) w[(size_t)i] = pfb_tune_entry(i, q);
+        p->tune_q = 0;
+        STAGE_HIP(p, hipMemcpyAsync(p->d_tune_w, w.data(), w.size() * sizeof(float2), hipMemcpyHostToDevice, p->stream));
+        STAGE_HIP(p, hipStreamSynchronize(p->stream));
+    }
+    STAGE_HIP(p, hipMemcpyAsync(p->d_tune_step, steps, (size_t)count * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    STAGE_HIP(p, hipStreamSynchronize(p->stream));
+    p->tune_q = q;
+    p->tune_steps.assign(steps, steps + count);
+    return RFA_OK;
+}
+
+int rfa_pfb_get_tuning(const rfa_pfb *p, int32_t *q, int32_t *steps, size_t capacity, int32_t *count) {
+    if (!p) return RFA_ERR_INVALID;
+    if (q) *q = p->tune_q;
+    if (count) *count = (int32_t)p->tune_steps.size();
+    if (steps) {
+        if (capacity < p->tune_steps.size()) return RFA_ERR_SIZE;
+        std::memcpy(steps, p->tune_steps.data(), p->tune_steps.size() * sizeof(int32_t));
+    }
+    return RFA_OK;
+}
+
+int rfa_pfb_tuning_index(int32_t q, int32_t step, uint64_t n, int32_t *i) {
+    if (!i || !pfb_tune_q_valid(q) || step <= -q || step >= q || n >= (uint64_t)1 << 53) return RFA_ERR_INVALID;
+    *i = (int32_t)pfb_tune_index((unsigned)q, pfb_tune_mu((unsigned)q), step, n);
+    return RFA_OK;
+}
+
+int rfa_pfb_tuning_table(int32_t q, float *cos_t, float *sin_t, size_t capacity) {
+    if (!pfb_tune_q_valid(q) || !cos_t || !sin_t) return RFA_ERR_INVALID;
+    if (capacity < (size_t)q) return RFA_ERR_SIZE;
+    for (int32_t j = 0; j < q; j++) {
+        const float2 w = pfb_tune_entry(j, q);
+        cos_t[j] = w.x;
+        sin_t[j] = w.y;
+    }
     return RFA_OK;
 }
 
@@ -718,6 +903,12 @@ int rfa_pfb_process(rfa_pfb *p, const void *in, size_t n_samples, float *out_re,
     STAGE_HIP(p, hipSetDevice(p->device));
     const hipError_t e = stage_dispatch_format(p->fmt, [&](auto f) {
         constexpr int FMT = decltype(f)::value;
+        if (p->tune_q) {                               // the tuned siblings, same grid and LDS: still two launches
+            const PfbTune t{p->d_tune_w, p->d_tune_step, (unsigned)p->tune_q, pfb_tune_mu((unsigned)p->tune_q)};
+            return p->rational ? pfb_launch<FMT>(pfb_rational_kernel<FMT, PfbRatTunedLaunch>, PfbRatTunedLaunch{b, t}, a,
+                                                 p->stream)
+                               : pfb_launch<FMT>(pfb_kernel<FMT, PfbTunedLaunch>, PfbTunedLaunch{a, t}, a, p->stream);
+        }
         return p->rational ? pfb_launch<FMT>(pfb_rational_kernel<FMT>, b, a, p->stream)
                            : pfb_launch<FMT>(pfb_kernel<FMT>, a, a, p->stream);
     });

@@ -32,7 +32,9 @@ two banks.
 ``Channelizer`` is the front end for channels on a uniform raster (``rfa_pfb_*``): a polyphase
 filter bank that gives all M channels k * Fs / M of one raw stream in two launches per call,
 for a cost that does not grow with the channel count; ``RasterReceiverBank`` chains it into a
-``DemodulatorBank``.
+``DemodulatorBank``.  ``Channelizer.for_channels`` with ``set_offsets`` receives channels that are off
+the raster through their nearest raster channel (a per-slot rotation fused into the channelizer's
+store); ``TunedReceiverBank`` is that chain with ``ReceiverBank``'s interface.
 
 ``SquelchBank`` is the per-channel squelch of the bank chains (``rfa_squelch_*``): a level meter
 on the quadrature rows and the Scheduler's squelch rule with its debounce per slot; a bank chain
@@ -1078,8 +1080,9 @@ class Channelizer(_Handle):
     8 ... 4096; 1 <= ``decimation`` <= M; up to 16 * M taps.  Channel k is the stream mixed down
     by k * Fs / M (k >= M/2: the negative offsets), filtered and decimated; ``set_channels``
     picks which channels are written, slot j being channel ``channels[j]``.  The output rows are
-    what ``DemodulatorBank.process_device`` reads.  Channels that are not on a raster stay with
-    ``FrontEndBank``."""
+    what ``DemodulatorBank.process_device`` reads.  A channel that is not on the raster is received
+    through its nearest raster channel: ``for_channels`` widens the prototype, ``nearest_channel``
+    picks the slot and ``set_offsets`` / ``set_tuning`` rotate it to DC inside the same launch."""
 
     _prefix = "rfa_pfb"
 
@@ -1163,6 +1166,40 @@ class Channelizer(_Handle):
             raise ValueError("the low-pass design rejected the raster")
         return cls(input_format, sample_rate // spacing_hz, sample_rate // output_rate, taps, device)
 
+    @staticmethod
+    def channels_design(sample_rate: int, spacing_hz: int, output_rate: int, passband_hz: float,
+                        resample: bool = False):
+        """((M, L, D), taps) of ``for_channels``: the raster of ``for_raster`` (L = 1) or
+        ``for_raster_resampled``, and the prototype with pass edge fp = ``passband_hz`` and stop edge
+        fs = ``output_rate / 2`` (where the output rate's own aliases begin):
+        ``create_low_pass_taps(L, L * sample_rate, (fp + fs) / 2, fs - fp, 60)``.  ``ValueError``
+        where fp >= fs or a channelizer limit fails.  Host only."""
+        sample_rate, spacing_hz, output_rate = int(sample_rate), int(spacing_hz), int(output_rate)
+        M, L, D = Channelizer.raster_ratio(sample_rate, spacing_hz, output_rate)
+        if not resample and L != 1:
+            raise ValueError("sample_rate must be a whole multiple of output_rate (or resample=True)")
+        fp, fs = float(passband_hz), output_rate / 2
+        if not 0 < fp < fs:
+            raise ValueError(f"passband_hz {fp} must lie inside (0, output_rate / 2 = {fs})")
+        taps = create_low_pass_taps(L, L * sample_rate, (fp + fs) / 2, fs - fp, 60)
+        if taps is None:
+            raise ValueError("the low-pass design rejected the raster")
+        if taps.size > 16 * M * L:
+            raise ValueError(f"prototype of {taps.size} taps above 16 * {M} * {L}")
+        return (M, L, D), taps
+
+    @classmethod
+    def for_channels(cls, input_format: str, sample_rate: int, spacing_hz: int, output_rate: int, passband_hz: float,
+                     device: int = 0, resample: bool = False):
+        """The channelizer for receivers at any frequency: the raster of ``for_raster`` (or, with
+        ``resample``, of ``for_raster_resampled``) with a prototype wide enough that a signal up to
+        ``passband_hz`` from a raster centre passes (``channels_design``); ``set_offsets`` then moves
+        it to DC and the demodulator's own filter selects the channel."""
+        (M, L, D), taps = cls.channels_design(sample_rate, spacing_hz, output_rate, passband_hz, resample)
+        if resample:
+            return cls.rational(input_format, M, L, D, taps, device)
+        return cls(input_format, M, D, taps, device)
+
     # -- configuration
     def set_channels(self, channels=None) -> None:
         """Slot j is channel ``channels[j]`` (any order, repeats allowed); None or empty: all
@@ -1187,6 +1224,74 @@ class Channelizer(_Handle):
             raise ValueError(f"offset {int(channel_frequency) - int(frequency)} Hz is not on the raster of "
                              f"{sample_rate}/{self.n_channels} Hz")
         return (num // int(sample_rate)) % self.n_channels
+
+    @staticmethod
+    def nearest_raster_channel(n_channels: int, frequency: int, channel_frequency: int, sample_rate: int):
+        """``nearest_channel`` for a raster of ``n_channels``, without a handle.  Host only."""
+        M, fs = int(n_channels), int(sample_rate)
+        if M <= 0 or fs <= 0 or fs % M:
+            raise ValueError(f"the spacing {sample_rate}/{n_channels} Hz must be a whole number of Hz")
+        spacing = fs // M
+        offset = int(channel_frequency) - int(frequency)
+        if 2 * abs(offset) > fs:
+            raise ValueError(f"offset {offset} Hz is outside the stream's +-{fs / 2} Hz")
+        k = (2 * offset + spacing) // (2 * spacing)                # floor((offset + spacing / 2) / spacing)
+        return k % M, offset - k * spacing
+
+    def nearest_channel(self, frequency: int, channel_frequency: int, sample_rate: int) -> tuple[int, int]:
+        """(k, delta_hz): the raster channel nearest to ``channel_frequency`` when the stream is tuned
+        to ``frequency``, and what is left for ``set_offsets``: k = floor((offset + spacing / 2) /
+        spacing) mod M with spacing = sample_rate / n_channels (a whole number of Hz), delta = offset -
+        (unwrapped k) * spacing in [-spacing / 2, spacing / 2).  ``ValueError`` where |offset| >
+        sample_rate / 2.  Host only."""
+        return self.nearest_raster_channel(self.n_channels, frequency, channel_frequency, sample_rate)
+
+    @staticmethod
+    def offsets_tuning(offsets_hz, output_rate: int) -> tuple[int, list[int]]:
+        """(q, steps) of ``set_offsets``: g = gcd(output_rate, |offsets| ...), q = output_rate / g,
+        m_j = offset_j / g, so that m_j * output_rate / q is offset_j exactly.  ``ValueError`` for a
+        non-integer offset, |offset| >= output_rate, or q above ``RFA_PFB_TUNE_MAX_STEPS``.  Host only."""
+        rate = int(output_rate)
+        if rate <= 0:
+            raise ValueError("output_rate must be positive")
+        offs = []
+        for o in offsets_hz:
+            if int(o) != o:
+                raise ValueError(f"offset {o!r} is not a whole number of Hz")
+            offs.append(int(o))
+        g = math.gcd(rate, *[abs(o) for o in offs])
+        q = rate // g
+        if q > _lib.RFA_PFB_TUNE_MAX_STEPS:
+            raise ValueError(f"tuning denominator {q} above {_lib.RFA_PFB_TUNE_MAX_STEPS}")
+        if any(abs(o) >= rate for o in offs):
+            raise ValueError(f"an offset of {output_rate} Hz or more cannot be tuned at that output rate")
+        return q, [o // g for o in offs]
+
+    def set_tuning(self, q: int = 0, steps=None) -> None:
+        """Slot j is rotated by exp(-2 pi j steps[j] n / q) on its way out, n the absolute output
+        index (``rfa_pfb_set_tuning``): a signal steps[j] * output_rate / q Hz above the raster centre
+        lands at DC.  One step per selected slot, -q < step < q, 1 <= q <= 2^20; q = 0 or steps None
+        removes the tuning.  An invalid request raises and leaves the tuning as it was;
+        ``set_channels`` removes it."""
+        if steps is None or not q:
+            self._call("set_tuning", 0, None, 0)
+            return
+        st = [int(m) for m in steps]
+        arr = (ctypes.c_int32 * max(len(st), 1))(*st)
+        self._call("set_tuning", int(q), arr, len(st))
+
+    @property
+    def tuning(self):
+        """None, or (q, steps) as given to ``set_tuning``."""
+        q, n = ctypes.c_int32(0), ctypes.c_int32(0)
+        out = (ctypes.c_int32 * self.n_channels)()
+        self._call("get_tuning", ctypes.byref(q), out, self.n_channels, ctypes.byref(n))
+        return (q.value, list(out[:n.value])) if q.value else None
+
+    def set_offsets(self, offsets_hz, output_rate: int) -> None:
+        """Slot j receives ``offsets_hz[j]`` (whole Hz) above its raster centre: ``set_tuning`` with
+        the smallest table that holds every offset exactly (``offsets_tuning``)."""
+        self.set_tuning(*self.offsets_tuning(offsets_hz, output_rate))
 
     def plan(self) -> dict:
         """{"n_channels", "decimation", "num_taps", "radices"}: the DFT's radices in stage order."""
@@ -1286,3 +1391,64 @@ class RasterReceiverBank(_BankChain):
     @property
     def channels(self) -> list[int]:
         return self.front.channels
+
+
+class TunedReceiverBank(_BankChain):
+    """Raw IQ bytes -> one audio stream per channel at any frequency, with ``ReceiverBank``'s
+    interface and the channelizer's cost: a ``Channelizer.for_channels`` on the raster of
+    ``spacing_hz`` at the modes' common quadrature rate feeding a ``DemodulatorBank``, 2 + 4 launches
+    per packet whatever the channel count.  ``set_frequencies`` gives every slot its nearest raster
+    channel and the offset that is left (up to half a spacing) as a tuning, so the slot's signal
+    sits at DC as behind a ``FrontEndBank``; the demodulator's user filter selects the channel.
+    ``passband_hz`` is the prototype's pass edge: by default half a spacing plus the widest
+    ``max_width`` of the modes (the widths are one-sided cut-offs, Demodulator.kt:215-226).  Slot
+    k's audio equals, bit for bit, a ``DemodulatorBank`` fed the output of a ``for_channels`` handle
+    with the same selection and offsets; with a squelch the level is measured on the tuned rows.
+    Until ``set_frequencies`` is called the slots are raster channels 0, 1, ... untuned."""
+
+    def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, device: int = 0,
+                 resample: bool = False, *, squelch=None, passband_hz: float | None = None):
+        modes, rate = _common_rate(modes)
+        if passband_hz is None:
+            passband_hz = int(spacing_hz) / 2 + max(mode_info(m)[2] for m in modes)
+        self.passband_hz = float(passband_hz)
+        self._resample = bool(resample)
+        super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch)
+
+    def _make_front(self, spacing_hz: int):
+        front = Channelizer.for_channels(self.input_format, self.sample_rate, spacing_hz, self.quadrature_rate,
+                                         self.passband_hz, self.device, self._resample)
+        try:
+            front.set_channels(range(self.n_channels))
+        except Exception:
+            front.close()
+            raise
+        return front
+
+    def _capacity(self, n: int) -> int:
+        if self._resample:                            # ceil(c1 L / D) - ceil(c0 L / D) <= ceil(n L / D)
+            return -(-n * self.front.interpolation // self.front.decimation) + 1
+        return n // self.front.decimation + 1         # an upper bound of any call of n samples
+
+    def set_frequencies(self, frequency: int, channel_frequencies) -> None:
+        """The source's tuned frequency and one channel frequency per slot, whole Hz, each within the
+        stream's +- sample_rate / 2."""
+        freqs = [int(f) for f in channel_frequencies]
+        if len(freqs) != self.n_channels:
+            raise ValueError(f"{self.n_channels} channel frequencies expected, got {len(freqs)}")
+        near = [self.front.nearest_channel(frequency, f, self.sample_rate) for f in freqs]
+        tuning = Channelizer.offsets_tuning([d for _, d in near], self.quadrature_rate)   # raises before any change
+        self.front.set_channels([k for k, _ in near])
+        self.front.set_tuning(*tuning)
+
+    @property
+    def channels(self) -> list[int]:
+        return self.front.channels
+
+    @property
+    def offsets(self) -> list[int]:
+        """Every slot's offset from its raster centre in Hz."""
+        t = self.front.tuning
+        if t is None:
+            return [0] * self.n_channels
+        return [m * self.quadrature_rate // t[0] for m in t[1]]
