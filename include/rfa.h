@@ -711,6 +711,33 @@ RFA_API int rfa_pfb_get_ratio(const rfa_pfb *p, int32_t *interpolation, int32_t 
  * L > D, gcd != 1), a null n, or consumed + n_samples >= 2^53. */
 RFA_API int rfa_pfb_rational_outputs(int32_t interpolation, int32_t decimation, uint64_t consumed, size_t n_samples,
                                      size_t *n);
+/* Host only, no handle and no device needed: the workgroup tile plan every
+ * rfa_pfb_process call of such a handle launches with (the same planning code
+ * the launch runs).  interpolation 0 asks for the handle of rfa_pfb_create,
+ * interpolation >= 1 for that of rfa_pfb_create_rational (1 included);
+ * num_taps is the prototype's length T.  plan receives RFA_PFB_PLAN_FIELDS
+ * values, indexed by rfa_pfb_plan_field.  RFA_ERR_INVALID for a null plan, a
+ * negative interpolation and whatever the matching create entry refuses as
+ * invalid, then RFA_ERR_UNSUPPORTED for an n_channels rfa_pfb_supported
+ * rejects; nothing is written on an error. */
+enum rfa_pfb_plan_field {
+    RFA_PFB_PLAN_TIMES = 0,         /* NT: output times per workgroup, a power of two */
+    RFA_PFB_PLAN_PITCH = 1,         /* Mp: LDS row pitch in points, n_channels | 1 */
+    RFA_PFB_PLAN_RUN = 2,           /* samples a full workgroup depends on */
+    RFA_PFB_PLAN_STAGED_RUN = 3,    /* 1: the run is staged in LDS; 0: the fold reads history and raw buffer */
+    RFA_PFB_PLAN_STAGED_TAPS = 4,   /* rfa_pfb_create: 1 where the taps are staged (with the run), else 0;
+                                       rational: the number of tap rows staged behind the run, 0 for none */
+    RFA_PFB_PLAN_ROWS_BY_TIME = 5,  /* rational: 1 where the staged tap rows are indexed by output time
+                                       (interpolation > NT), 0 where by phase or where none is staged */
+    RFA_PFB_PLAN_STAGE_POINTS = 6,  /* 8-byte points of LDS in front of the DFT rows: staged run + taps */
+    RFA_PFB_PLAN_LDS_BYTES = 7,     /* dynamic LDS of one workgroup as launched */
+    RFA_PFB_PLAN_STAGES = 8,        /* DFT stages */
+    RFA_PFB_PLAN_RADIX0 = 9,        /* their radices in stage order, RFA_PFB_PLAN_MAX_STAGES slots, 0 past the last */
+    RFA_PFB_PLAN_FIELDS = 21
+};
+#define RFA_PFB_PLAN_MAX_STAGES 12
+RFA_API int rfa_pfb_tile_plan(int32_t n_channels, int32_t interpolation, int32_t decimation, int32_t num_taps,
+                              int32_t *plan);
 
 /* Fine tuning: receivers at any frequency, not only on the
  * raster.  A handle of either create entry may carry a tuning: a denominator Q

@@ -227,6 +227,7 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_pfb_get_ratio": (ctypes.c_int, [_h] + [ctypes.POINTER(ctypes.c_int32)] * 3),
         "rfa_pfb_rational_outputs": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_size_t,
                                                     ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_pfb_tile_plan": (ctypes.c_int, [ctypes.c_int32] * 4 + [ctypes.POINTER(ctypes.c_int32)]),
         "rfa_pfb_set_tuning": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
         "rfa_pfb_get_tuning": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                               ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),

@@ -521,6 +521,13 @@ void pfb_plan_rational(PfbRatLaunch &b) {
     a.stage = b.stage_x ? a.run + (b.tap_rows ? (int)tap_points : 0) : 0;
 }
 
+// The plan of a call's record (b.a.T = taps per output, b.a.M, b.a.D and b.L set): what
+// rfa_pfb_process launches with and what rfa_pfb_tile_plan reports.
+void pfb_plan(PfbRatLaunch &b, bool rational) {
+    if (rational) pfb_plan_rational(b);
+    else pfb_plan_tile(b.a);
+}
+
 long long pfb_gcd(long long a, long long b) {
     while (b) {
         const long long t = a % b;
@@ -528,6 +535,18 @@ long long pfb_gcd(long long a, long long b) {
         b = t;
     }
     return a;
+}
+
+// What rfa_pfb_create refuses as invalid in (M, D, T), and rfa_pfb_create_rational in (M, L, D, T).
+bool pfb_integer_args_valid(int32_t M, int32_t D, int32_t T) {
+    if (M < 1 || D < 1 || T < 1) return false;
+    return D <= M && (long long)T <= (long long)RFA_PFB_MAX_PHASES * M;
+}
+
+bool pfb_rational_args_valid(int32_t M, int32_t L, int32_t D, int32_t T) {
+    if (M < 1 || L < 1 || D < 1 || T < 1) return false;
+    return L <= RFA_PFB_MAX_INTERPOLATION && L <= D && (long long)D <= (long long)L * M && pfb_gcd(L, D) == 1 &&
+           (long long)T <= (long long)RFA_PFB_MAX_PHASES * M * L;
 }
 
 // Outputs due once c samples are consumed: ceil(c * L / D); c < 2^53 and L <= 64 keep the product in range.
@@ -662,9 +681,7 @@ int rfa_pfb_create(int device, int input_format, int32_t n_channels, int32_t dec
                    int32_t num_taps, rfa_pfb **out) {
     if (!out) return RFA_ERR_INVALID;
     *out = nullptr;
-    if (stage_sample_bytes(input_format) == 0 || n_channels < 1 || decimation < 1 || !taps || num_taps < 1)
-        return RFA_ERR_INVALID;
-    if (decimation > n_channels || (long long)num_taps > (long long)RFA_PFB_MAX_PHASES * n_channels)
+    if (stage_sample_bytes(input_format) == 0 || !taps || !pfb_integer_args_valid(n_channels, decimation, num_taps))
         return RFA_ERR_INVALID;
     return pfb_create(device, input_format, n_channels, 1, decimation, false, taps, num_taps, out);
 }
@@ -673,12 +690,8 @@ int rfa_pfb_create_rational(int device, int input_format, int32_t n_channels, in
                             const float *taps, int32_t num_taps, rfa_pfb **out) {
     if (!out) return RFA_ERR_INVALID;
     *out = nullptr;
-    if (stage_sample_bytes(input_format) == 0 || n_channels < 1 || interpolation < 1 || decimation < 1 || !taps ||
-        num_taps < 1)
-        return RFA_ERR_INVALID;
-    if (interpolation > RFA_PFB_MAX_INTERPOLATION || interpolation > decimation ||
-        (long long)decimation > (long long)interpolation * n_channels || pfb_gcd(interpolation, decimation) != 1 ||
-        (long long)num_taps > (long long)RFA_PFB_MAX_PHASES * n_channels * interpolation)
+    if (stage_sample_bytes(input_format) == 0 || !taps ||
+        !pfb_rational_args_valid(n_channels, interpolation, decimation, num_taps))
         return RFA_ERR_INVALID;
     return pfb_create(device, input_format, n_channels, interpolation, decimation, true, taps, num_taps, out);
 }
@@ -699,6 +712,36 @@ int rfa_pfb_rational_outputs(int32_t interpolation, int32_t decimation, uint64_t
     if (consumed >= lim || (uint64_t)n_samples >= lim || consumed + (uint64_t)n_samples >= lim) return RFA_ERR_INVALID;
     *n = (size_t)(pfb_rational_count((long long)(consumed + n_samples), interpolation, decimation) -
                   pfb_rational_count((long long)consumed, interpolation, decimation));
+    return RFA_OK;
+}
+
+int rfa_pfb_tile_plan(int32_t n_channels, int32_t interpolation, int32_t decimation, int32_t num_taps, int32_t *plan) {
+    static_assert(RFA_PFB_PLAN_MAX_STAGES == kPfbMaxStages &&
+                  RFA_PFB_PLAN_FIELDS == RFA_PFB_PLAN_RADIX0 + RFA_PFB_PLAN_MAX_STAGES);
+    const bool rational = interpolation != 0;
+    if (!plan) return RFA_ERR_INVALID;
+    if (rational ? !pfb_rational_args_valid(n_channels, interpolation, decimation, num_taps)
+                 : !pfb_integer_args_valid(n_channels, decimation, num_taps))
+        return RFA_ERR_INVALID;
+    const std::vector<int> radix = pfb_radices(n_channels);
+    if (radix.empty()) return RFA_ERR_UNSUPPORTED;
+    PfbRatLaunch b{};                                  // the record rfa_pfb_process fills, as pfb_create sizes it
+    PfbLaunch &a = b.a;
+    b.L = rational ? interpolation : 1;
+    a.T = (num_taps + b.L - 1) / b.L;
+    a.M = n_channels;
+    a.D = decimation;
+    pfb_plan(b, rational);
+    plan[RFA_PFB_PLAN_TIMES] = a.NT;
+    plan[RFA_PFB_PLAN_PITCH] = a.Mp;
+    plan[RFA_PFB_PLAN_RUN] = a.run;
+    plan[RFA_PFB_PLAN_STAGED_RUN] = rational ? b.stage_x : a.stage != 0;
+    plan[RFA_PFB_PLAN_STAGED_TAPS] = rational ? b.tap_rows : a.stage != 0;
+    plan[RFA_PFB_PLAN_ROWS_BY_TIME] = rational && b.tap_rows && b.L > a.NT;   // pfb_rational_kernel's !by_phase
+    plan[RFA_PFB_PLAN_STAGE_POINTS] = a.stage;
+    plan[RFA_PFB_PLAN_LDS_BYTES] = pfb_lds_bytes(a);
+    plan[RFA_PFB_PLAN_STAGES] = (int32_t)radix.size();
+    for (int s = 0; s < kPfbMaxStages; s++) plan[RFA_PFB_PLAN_RADIX0 + s] = s < (int)radix.size() ? radix[s] : 0;
     return RFA_OK;
 }
 
@@ -882,13 +925,8 @@ int rfa_pfb_process(rfa_pfb *p, const void *in, size_t n_samples, float *out_re,
     a.M = p->M;
     a.D = p->D;
     b.L = p->L;
-    if (p->rational) {
-        pfb_plan_rational(b);
-        a.n0 = pfb_rational_count(p->in_done, p->L, p->D);
-    } else {
-        pfb_plan_tile(a);
-        a.n0 = p->in_done / p->D;
-    }
+    pfb_plan(b, p->rational);
+    a.n0 = p->rational ? pfb_rational_count(p->in_done, p->L, p->D) : p->in_done / p->D;
     a.in0 = p->in_done;
     a.n_out = n;
     a.tw = p->d_tw;

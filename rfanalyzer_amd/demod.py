@@ -1072,6 +1072,26 @@ class ReceiverBank(_BankChain):
 
 # ---------------------------------------------------------------- polyphase channelizer
 
+PFB_PLAN_FIELDS = ("NT", "Mp", "run", "staged_run", "staged_taps", "rows_by_time", "stage_points", "lds_bytes",
+                   "stages")                                # rfa_pfb_plan_field order; the radices follow
+PFB_PLAN_MAX_STAGES = 12
+
+
+def pfb_tile_plan(n_channels: int, interpolation: int, decimation: int, num_taps: int) -> dict:
+    """The workgroup tile plan of a channelizer (``rfa_pfb_tile_plan``): output times per workgroup
+    ``NT``, LDS row pitch ``Mp``, the ``run`` of samples a workgroup depends on, ``staged_run`` (0 / 1),
+    ``staged_taps`` (integer handle: 0 / 1; rational: staged tap rows), ``rows_by_time`` (0 / 1),
+    ``stage_points``, ``lds_bytes`` as launched, ``stages`` and the list ``radices``.  ``interpolation``
+    0 is the handle of ``Channelizer(...)``, >= 1 that of ``Channelizer.rational``; ``num_taps`` is the
+    prototype's length.  Host-only."""
+    out = (ctypes.c_int32 * (len(PFB_PLAN_FIELDS) + PFB_PLAN_MAX_STAGES))()
+    _lib.check(_lib.lib().rfa_pfb_tile_plan(n_channels, interpolation, decimation, num_taps, out),
+               "rfa_pfb_tile_plan")
+    plan = dict(zip(PFB_PLAN_FIELDS, (int(v) for v in out)))
+    plan["radices"] = [int(v) for v in out[len(PFB_PLAN_FIELDS):len(PFB_PLAN_FIELDS) + plan["stages"]]]
+    return plan
+
+
 class Channelizer(_Handle):
     """All ``n_channels`` = M channels of the uniform raster k * Fs / M out of one raw IQ stream
     per call (``rfa_pfb_*``, ``rfanalyzer_amd/csrc/channelizer.hip``): the prototype low-pass

@@ -1,5 +1,6 @@
 // Host-side check of the polyphase channelizer's C-ABI entries that need no
-// device: the length rule and every error path that returns before any HIP call.
+// device: the length rule, the tile-plan query over every supported length, and
+// every error path that returns before any HIP call.
 // Built together with rfanalyzer_amd/csrc/channelizer.hip with the host compiled
 // under AddressSanitizer and UBSan (tools/Makefile) and run as an ordinary
 // program; exits 0 when every check holds.
@@ -103,10 +104,84 @@ static void check_null_handle() {
     CHECK(w[0] == 9 && w[3] == 9 && n[0] == 9 && n[1] == 9 && f[0] == 9.0f && f[1] == 9.0f);
 }
 
+// rfa_pfb_tile_plan over every supported M with a grid of (L, D, T) at the limits of the create
+// entries: the invariants every plan has, whatever the planning rule is, and the argument errors.
+static void check_tile_plan() {
+    constexpr int F = RFA_PFB_PLAN_FIELDS;
+    int32_t guard[F + 2];
+    int32_t *w = guard + 1;
+    auto fill = [&] { for (int i = 0; i < F + 2; i++) guard[i] = -77; };
+    auto untouched = [&] {
+        for (int i = 0; i < F + 2; i++)
+            if (guard[i] != -77) return false;
+        return true;
+    };
+    long plans = 0;
+    for (int32_t m = RFA_PFB_MIN_CHANNELS; m <= RFA_PFB_MAX_CHANNELS; m++) {
+        if (!smooth(m)) continue;
+        for (int32_t l : {0, 1, 2, 3, 17, RFA_PFB_MAX_INTERPOLATION}) {
+            const long long lm = (long long)(l ? l : 1) * m;
+            const int32_t ds[] = {l ? l : 1, (l ? l : 1) + 1, (int32_t)(lm / 2) + 1, (int32_t)lm - 1, (int32_t)lm};
+            const int32_t ts[] = {1, m - 1, m, 2 * m + 1, (int32_t)(RFA_PFB_MAX_PHASES * lm)};
+            for (int32_t d : ds)
+                for (int32_t t : ts) {
+                    fill();
+                    const int st = rfa_pfb_tile_plan(m, l, d, t, w);
+                    if (st != RFA_OK) {                     // a (L, D) of the grid with a common factor
+                        CHECK(st == RFA_ERR_INVALID && l > 1 && untouched());
+                        continue;
+                    }
+                    plans++;
+                    CHECK(guard[0] == -77 && guard[F + 1] == -77);
+                    const int nt = w[RFA_PFB_PLAN_TIMES], mp = w[RFA_PFB_PLAN_PITCH];
+                    CHECK(nt >= 1 && nt <= 16 && (nt & (nt - 1)) == 0 && nt * m <= 4096 && (nt == 16 || 2 * nt * m > 4096));
+                    CHECK(mp >= m && mp % 2 == 1 && mp <= m + 1);
+                    CHECK(w[RFA_PFB_PLAN_LDS_BYTES] == 8 * (w[RFA_PFB_PLAN_STAGE_POINTS] + 2 * nt * mp));
+                    CHECK(w[RFA_PFB_PLAN_LDS_BYTES] <= 64 * 1024 + 2 * (4096 + 16) * 8);   // what the kernels are prepared for
+                    CHECK(w[RFA_PFB_PLAN_STAGED_RUN] == 0 || w[RFA_PFB_PLAN_STAGED_RUN] == 1);
+                    CHECK((w[RFA_PFB_PLAN_STAGE_POINTS] != 0) == (w[RFA_PFB_PLAN_STAGED_RUN] == 1));
+                    CHECK(w[RFA_PFB_PLAN_STAGED_RUN] == 0 || w[RFA_PFB_PLAN_STAGE_POINTS] >= w[RFA_PFB_PLAN_RUN]);
+                    CHECK(w[RFA_PFB_PLAN_STAGED_TAPS] >= 0 && w[RFA_PFB_PLAN_STAGED_TAPS] <= (l ? nt : 1));
+                    CHECK(w[RFA_PFB_PLAN_STAGED_TAPS] == 0 || w[RFA_PFB_PLAN_STAGED_RUN] == 1);
+                    CHECK(w[RFA_PFB_PLAN_ROWS_BY_TIME] == (l > nt && w[RFA_PFB_PLAN_STAGED_TAPS] > 0 ? 1 : 0));
+                    const int ns = w[RFA_PFB_PLAN_STAGES];
+                    CHECK(ns >= 1 && ns <= RFA_PFB_PLAN_MAX_STAGES);
+                    long long prod = 1;
+                    for (int s = 0; s < RFA_PFB_PLAN_MAX_STAGES; s++) {
+                        const int r = w[RFA_PFB_PLAN_RADIX0 + s];
+                        if (s < ns) {
+                            CHECK(r >= 2 && r <= 5);
+                            prod *= r;
+                        } else {
+                            CHECK(r == 0);
+                        }
+                    }
+                    CHECK(prod == m);
+                }
+        }
+    }
+    CHECK(plans > 10000);
+    // argument errors: the create entries' rules, invalid before unsupported, nothing written
+    fill();
+    CHECK(rfa_pfb_tile_plan(16, 0, 4, 16, nullptr) == RFA_ERR_INVALID);
+    const int32_t bad[][4] = {{0, 0, 1, 16},   {-16, 0, 1, 16}, {16, 0, 0, 16},  {16, 0, -3, 16},  {16, 0, 17, 16},
+                              {16, 0, 4, 0},   {16, 0, 4, -1},  {16, 0, 4, 257}, {16, -1, 4, 16},  {7, 0, 0, 8},
+                              {16, 65, 66, 61}, {16, 8, 7, 61}, {16, 3, 49, 61}, {16, 6, 14, 61},  {16, 3, 7, 769},
+                              {16, 3, 0, 61},  {0, 3, 7, 61},   {16, 3, 7, 0},   {7, 3, 22, 61}};
+    for (const auto &a : bad) CHECK(rfa_pfb_tile_plan(a[0], a[1], a[2], a[3], w) == RFA_ERR_INVALID && untouched());
+    for (int32_t m : {1, 7, 14, 22, 4097, 8192}) {
+        CHECK(rfa_pfb_tile_plan(m, 0, 1, 8, w) == RFA_ERR_UNSUPPORTED && untouched());
+        CHECK(rfa_pfb_tile_plan(m, 1, 1, 8, w) == RFA_ERR_UNSUPPORTED && untouched());
+    }
+    CHECK(rfa_pfb_tile_plan(16, 0, 16, 256, w) == RFA_OK && rfa_pfb_tile_plan(16, 3, 47, 768, w) == RFA_OK);
+    CHECK(rfa_pfb_tile_plan(16, 64, 65, 61, w) == RFA_OK);
+}
+
 int main() {
     check_supported();
     check_create_errors();
     check_null_handle();
+    check_tile_plan();
     if (failures) {
         std::fprintf(stderr, "pfb_host_check: %d check(s) failed\n", failures);
         return 1;
