@@ -35,6 +35,7 @@
  *     analyzer/Scheduler.kt:52,161-165,237, database/AppStateRepository.kt:318-324
  *   (extension) every channel of a uniform raster per call rfa_pfb_*() (polyphase channelizer, below;
  *     rfa_pfb_create_rational: at any source sample rate)
+ *   (extension) frequency error of every bank slot         rfa_freq_*() (frequency meter bank, below)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -1007,6 +1008,72 @@ RFA_API int rfa_squelch_get_state(const rfa_squelch *s, double *sums, float *lev
 RFA_API int rfa_squelch_set_stream(rfa_squelch *s, void *stream);
 RFA_API int rfa_squelch_get_stream(const rfa_squelch *s, void **stream);
 RFA_API int rfa_squelch_synchronize(rfa_squelch *s);
+
+/* ------------------------------------------------------------------------
+ * Frequency meter bank: where the signal of each of n_channels slots sits
+ * relative to the slot's centre, from the quadrature rows the squelch bank
+ * reads.  The reference tunes one channel by hand and has nothing like it.
+ *
+ * A call gives slot k the n samples x[i] = (re[i], im[i]) of its row and
+ * produces the lag-1 autocorrelation
+ *     R1 = sum of x[i] * conj(x[i-1])
+ *     R1_re = sum (re[i]*re[i-1] + im[i]*im[i-1])
+ *     R1_im = sum (im[i]*re[i-1] - re[i]*im[i-1])
+ * as two doubles: every product is formed in double from the float inputs (and
+ * is exact), a term is their sum rounded once, the terms are accumulated in
+ * double.  x[-1] is the slot's last sample of the previous call, kept on the
+ * device with a valid flag; without a valid one the term for i = 0 is left out.
+ * The number of terms of the call -- n, or n - 1 without a predecessor, 0 for
+ * n = 0 -- is reported per slot.  A carrier f Hz above the slot's centre gives
+ * arg R1 = 2 pi f / rate (rfa_freq_error_hz), unambiguous for |f| < rate / 2.
+ * A non-finite sample makes its slot's sums non-finite and touches no other slot.
+ *
+ * Which terms a lane and a tile sum, and the order of every addition, depend on
+ * i and n alone -- not on the row's address, channel_stride or n_channels -- and
+ * there are no atomics: a slot's sums are a function of its values, n and the
+ * carried sample, bit for bit.  n up to RFA_FREQ_TILE is one launch, above that
+ * a partials launch and a fold launch; n = 0 launches nothing, gives zero sums
+ * and keeps the carry.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_freq rfa_freq;
+
+#define RFA_FREQ_MAX_CHANNELS 1024             /* n_channels above this: RFA_ERR_INVALID */
+#define RFA_FREQ_TILE 16384                    /* samples of one workgroup; n up to this: one launch */
+
+/* Host only, no device: atan2(r1_im, r1_re) * rate / (2 pi).  0 for R1 = 0, NaN where a
+ * sum is not finite. */
+RFA_API double rfa_freq_error_hz(double r1_re, double r1_im, double rate);
+
+/* 1 <= n_channels <= RFA_FREQ_MAX_CHANNELS; arguments are checked before the device is
+ * looked for (as rfa_squelch_create).  No slot has a carry at first. */
+RFA_API int rfa_freq_create(int device, int32_t n_channels, rfa_freq **out);
+RFA_API int rfa_freq_destroy(rfa_freq *f);
+RFA_API const char *rfa_freq_last_error(const rfa_freq *f);
+RFA_API int rfa_freq_get_channels(const rfa_freq *f, int32_t *n_channels);
+/* Drops slot k's carry (k = -1: every slot's): its next call starts without a predecessor.
+ * For a slot whose phase is about to jump, such as one that was retuned.  A clear of the
+ * flag enqueued on the handle's stream, no synchronisation. */
+RFA_API int rfa_freq_break(rfa_freq *f, int32_t k);
+/* Drops every carry and the last results (sums and terms read 0). */
+RFA_API int rfa_freq_reset(rfa_freq *f);
+/* Device pointers; planar rows channel_stride floats apart (the layout of
+ * rfa_squelch_process).  Asynchronous: enqueues the launch(es), one copy of the
+ * 2 * n_channels sums into pinned memory and an event on the handle's stream, and returns.
+ * A steady-state call allocates nothing.  channel_stride below n_samples where
+ * n_channels > 1, or a NULL row with n_samples > 0, is RFA_ERR_INVALID. */
+RFA_API int rfa_freq_process(rfa_freq *f, const float *re, const float *im, size_t channel_stride,
+                             size_t n_samples);
+/* Waits for the last rfa_freq_process's event alone (not the stream) and hands out that call's
+ * sums and term counts, [n_channels] each; any pointer may be NULL.  Without a call since
+ * the last collect it waits for nothing and repeats the values. */
+RFA_API int rfa_freq_collect(rfa_freq *f, double *r1_re, double *r1_im, int64_t *terms);
+/* rfa_freq_process with host rows, then rfa_freq_collect: synchronous. */
+RFA_API int rfa_freq_process_host(rfa_freq *f, const float *re, const float *im, size_t channel_stride,
+                                  size_t n_samples, double *r1_re, double *r1_im, int64_t *terms);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_freq_set_stream(rfa_freq *f, void *stream);
+RFA_API int rfa_freq_get_stream(const rfa_freq *f, void **stream);
+RFA_API int rfa_freq_synchronize(rfa_freq *f);
 
 #ifdef __cplusplus
 }

@@ -302,6 +302,20 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_squelch_set_stream": (ctypes.c_int, [_h, _vp]),
         "rfa_squelch_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
         "rfa_squelch_synchronize": (ctypes.c_int, [_h]),
+        # frequency meter bank: lag-1 autocorrelation per slot (rfanalyzer_amd/csrc/freq.hip)
+        "rfa_freq_error_hz": (ctypes.c_double, [ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+        "rfa_freq_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_freq_destroy": (ctypes.c_int, [_h]),
+        "rfa_freq_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_freq_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_freq_break": (ctypes.c_int, [_h, ctypes.c_int32]),
+        "rfa_freq_reset": (ctypes.c_int, [_h]),
+        "rfa_freq_process": (ctypes.c_int, [_h, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t]),
+        "rfa_freq_collect": (ctypes.c_int, [_h, _vp, _vp, _vp]),
+        "rfa_freq_process_host": (ctypes.c_int, [_h, _vp, _vp, ctypes.c_size_t, ctypes.c_size_t, _vp, _vp, _vp]),
+        "rfa_freq_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_freq_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_freq_synchronize": (ctypes.c_int, [_h]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

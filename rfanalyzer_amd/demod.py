@@ -39,6 +39,11 @@ store); ``TunedReceiverBank`` is that chain with ``ReceiverBank``'s interface.
 ``SquelchBank`` is the per-channel squelch of the bank chains (``rfa_squelch_*``): a level meter
 on the quadrature rows and the Scheduler's squelch rule with its debounce per slot; a bank chain
 built with ``squelch=`` holds the demodulator slots whose gate is closed.
+
+``FrequencyMeterBank`` measures where each slot's signal sits relative to its centre (``rfa_freq_*``:
+the lag-1 autocorrelation of the quadrature rows, summed on the device); ``AfcRule`` is the
+per-slot control rule on the host, and ``ReceiverBank`` / ``TunedReceiverBank`` built with ``afc=``
+retune their slots with the two.  The reference has no counterpart.
 """
 from __future__ import annotations
 
@@ -777,6 +782,209 @@ class SquelchBank(_Handle):
         return {"sums": sums, "levels": levels, "counters": counters, "open": opn.astype(bool)}
 
 
+def frequency_error_hz(re: float, im: float, rate: float) -> float:
+    """``atan2(im, re) * rate / (2 pi)`` of a lag-1 autocorrelation (``rfa_freq_error_hz``): how far
+    above the slot's centre its signal sits.  0 for R1 = 0, NaN where a sum is not finite.  Host only."""
+    return float(_lib.lib().rfa_freq_error_hz(float(re), float(im), float(rate)))
+
+
+class FrequencyMeterBank(_Handle):
+    """Frequency-error meter for ``n_channels`` slots (``rfa_freq_*``, ``rfanalyzer_amd/csrc/freq.hip``).
+    A call sums every slot's lag-1 autocorrelation ``R1 = sum x[i] * conj(x[i-1])`` over its quadrature
+    row, in double, with the slot's last sample of the previous call as ``x[-1]`` (kept on the device;
+    ``break_`` drops it).  ``frequency_error_hz`` turns a pair of sums into Hz.  The sums are
+    bit-identical from run to run and for any placement of the rows.  ``process_device`` is
+    asynchronous; ``collect`` waits for its copy of the sums alone."""
+
+    _prefix = "rfa_freq"
+
+    def __init__(self, n_channels: int, device: int = 0):
+        self.n_channels = int(n_channels)
+        self._create("rfa_freq_create", device, self.n_channels)
+        self._re = np.zeros(self.n_channels, np.float64)
+        self._im = np.zeros(self.n_channels, np.float64)
+        self._terms = np.zeros(self.n_channels, np.int64)
+
+    def _out(self):
+        return self._re.ctypes.data, self._im.ctypes.data, self._terms.ctypes.data
+
+    def _result(self):
+        return self._re.copy(), self._im.copy(), self._terms.copy()
+
+    def break_(self, k: int | None = None) -> None:
+        """Drop slot k's carried sample (None: every slot's): its next call has one term less and no
+        predecessor.  For a slot whose phase is about to jump.  Ordered on the stream, no wait."""
+        self._call("break", -1 if k is None else int(k))
+
+    def reset(self) -> None:
+        """Drop every carry and the last results."""
+        self._call("reset")
+
+    def process_device(self, re_ptr: int, im_ptr: int, channel_stride: int, n_samples: int) -> None:
+        """Device pointers, rows ``channel_stride`` floats apart.  Enqueues the sums and their copy on
+        the handle's stream and returns; ``collect`` hands them out."""
+        self._call("process", re_ptr, im_ptr, channel_stride, n_samples)
+
+    def collect(self):
+        """(r1_re float64[K], r1_im float64[K], terms int64[K]) of the last ``process_device``; waits
+        for that call's copy and nothing else."""
+        self._call("collect", *self._out())
+        return self._result()
+
+    def process(self, re, im):
+        """Host planar float32 [K, n] -> (r1_re, r1_im, terms)."""
+        re = np.ascontiguousarray(re, np.float32)
+        im = np.ascontiguousarray(im, np.float32)
+        if re.shape != im.shape or re.ndim != 2 or re.shape[0] != self.n_channels:
+            raise ValueError(f"re and im must both have shape [{self.n_channels}, n]")
+        n = re.shape[1]
+        self._call("process_host", re.ctypes.data, im.ctypes.data, n, n, *self._out())
+        return self._result()
+
+    def process_tensor(self, re, im):
+        """torch.cuda float32 tensors [K, n] (rows may be slices of wider tensors) -> (r1_re, r1_im,
+        terms); on torch's current stream."""
+        self._follow_torch_stream(re)
+        K = self.n_channels
+        if re.shape != im.shape or re.dim() != 2 or re.shape[0] != K:
+            raise ValueError(f"re and im must have shape [{K}, n]")
+        if re.dtype != im.dtype or str(re.dtype) != "torch.float32":
+            raise ValueError("re and im must be float32")
+        for t in (re, im):
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("rows must be contiguous")
+        if K > 1 and re.stride(0) != im.stride(0):
+            raise ValueError("re and im must have the same row stride")
+        stride = re.stride(0) if K > 1 else re.shape[1]
+        self.process_device(re.data_ptr(), im.data_ptr(), stride, re.shape[1])
+        return self.collect()
+
+
+class AfcRule:
+    """Automatic frequency control for ``n_channels`` slots at quadrature rate ``rate``: what to do
+    with the sums of a ``FrequencyMeterBank``.  Host arithmetic only, no device.
+
+    ``update(r1_re, r1_im, active)`` adds the sums of the active slots into one double accumulator
+    pair per slot and counts the call.  On every ``interval``-th call each slot that was active at
+    least once turns its accumulated R1 into an error estimate ``err`` (``frequency_error_hz``); a
+    slot whose R1 is 0 or whose estimate is not finite is passed over.  ``err`` was measured while
+    the slot's applied correction ``a`` was in force, so the signal sits at ``a + err``, and the
+    rule moves its estimate ``c`` towards that: ``c <- clamp(c + gain * (a + err - c), +-limit_hz)``
+    -- for ``gain = 1`` the new estimate itself, and ``c + gain * err`` where ``c`` is what was
+    applied.  The applied correction is ``c`` rounded to the nearest multiple of ``step_hz`` (a tie
+    goes up), so a residual below half a step moves nothing and the output cannot hunt between two
+    multiples.  ``update`` returns the slots whose applied correction changed (an empty list
+    between intervals) and clears the accumulators.
+
+    ``step_hz = 25``, ``interval = 8`` and ``gain = 1`` are parameters chosen by hand, not
+    measurements: a step well below any mode's filter width, an interval of a few packets.
+    ``limit_hz`` (a number or one per slot) has no default here; the chains use half the mode's
+    default width."""
+
+    def __init__(self, n_channels: int, rate: float, *, step_hz: float = 25, limit_hz, interval: int = 8,
+                 gain: float = 1.0):
+        K = int(n_channels)
+        if K < 1:
+            raise ValueError("at least one slot")
+        if not (math.isfinite(rate) and rate > 0):
+            raise ValueError("rate must be positive")
+        if not (math.isfinite(step_hz) and step_hz > 0):
+            raise ValueError("step_hz must be positive")
+        if int(interval) != interval or interval < 1:
+            raise ValueError("interval must be a whole number of calls, at least 1")
+        if not (math.isfinite(gain) and 0 < gain <= 1):
+            raise ValueError("gain must lie in (0, 1]")
+        limit = np.array(np.broadcast_to(np.asarray(limit_hz, np.float64), (K,)))
+        if not (limit >= 0).all():
+            raise ValueError("limit_hz must be zero or more")
+        self.n_channels, self.rate = K, float(rate)
+        self.step_hz, self.interval, self.gain = float(step_hz), int(interval), float(gain)
+        self.limit_hz = limit
+        self._acc_re, self._acc_im = np.zeros(K), np.zeros(K)
+        self._seen = np.zeros(K, bool)
+        self._estimate, self._applied = np.zeros(K), np.zeros(K)
+        self._errors = np.full(K, np.nan)
+        self._calls = 0
+
+    @property
+    def corrections(self) -> np.ndarray:
+        """The applied correction per slot in Hz, multiples of ``step_hz`` (float64[K])."""
+        return self._applied.copy()
+
+    @property
+    def errors_hz(self) -> np.ndarray:
+        """Every slot's last error estimate in Hz (float64[K]); NaN before its first."""
+        return self._errors.copy()
+
+    def reset(self, k: int | None = None) -> None:
+        """Slot k (None: every slot, and the call count) back to no correction and no estimate."""
+        s = slice(None) if k is None else self._slot(k)
+        for a, v in ((self._acc_re, 0.0), (self._acc_im, 0.0), (self._seen, False), (self._estimate, 0.0),
+                     (self._applied, 0.0), (self._errors, np.nan)):
+            a[s] = v
+        if k is None:
+            self._calls = 0
+
+    def _slot(self, k: int) -> int:
+        if not 0 <= int(k) < self.n_channels:
+            raise ValueError(f"no slot {k}")
+        return int(k)
+
+    def update(self, r1_re, r1_im, active=None) -> list[int]:
+        K = self.n_channels
+        r1_re, r1_im = np.asarray(r1_re, np.float64), np.asarray(r1_im, np.float64)
+        act = np.ones(K, bool) if active is None else np.asarray(active, bool)
+        if r1_re.shape != (K,) or r1_im.shape != (K,) or act.shape != (K,):
+            raise ValueError(f"{K} sums and flags expected")
+        with np.errstate(all="ignore"):
+            self._acc_re[act] += r1_re[act]
+            self._acc_im[act] += r1_im[act]
+        self._seen |= act
+        self._calls += 1
+        if self._calls % self.interval:
+            return []
+        changed = []
+        for k in np.flatnonzero(self._seen):
+            re, im = self._acc_re[k], self._acc_im[k]
+            if re == 0.0 and im == 0.0:
+                continue
+            err = frequency_error_hz(re, im, self.rate)
+            if not math.isfinite(err):
+                continue
+            self._errors[k] = err
+            lim = self.limit_hz[k]
+            c = self._estimate[k] + self.gain * (self._applied[k] + err - self._estimate[k])
+            c = self._estimate[k] = min(max(c, -lim), lim)
+            applied = self.step_hz * math.floor(c / self.step_hz + 0.5)
+            if applied != self._applied[k]:
+                self._applied[k] = applied
+                changed.append(int(k))
+        self._acc_re[:] = 0.0
+        self._acc_im[:] = 0.0
+        self._seen[:] = False
+        return changed
+
+
+AFC_MODES = ("am", "nfm", "wfm")          # modes with a carrier at the slot's centre
+_AFC_MODE_IDS = frozenset(MODES[m] for m in AFC_MODES)
+
+
+def _afc_rule(afc, modes, rate: int):
+    """The ``afc=`` keyword of a bank chain -> (an ``AfcRule`` or None, whether ``limit_hz`` is the
+    default).  Host only: a wrong keyword raises before any handle is made."""
+    if afc is None or afc is False:
+        return None, False
+    if afc is True:
+        afc = {}
+    if not isinstance(afc, dict):
+        raise TypeError("afc must be None, True or a dict of AfcRule's keywords")
+    kw = dict(afc)
+    default_limit = "limit_hz" not in kw
+    if default_limit:
+        kw["limit_hz"] = [mode_info(m)[3] / 2 for m in modes]
+    return AfcRule(len(modes), rate, **kw), default_limit
+
+
 class _Chain:
     """What the receiver chains share: the context manager, the audio tensor and the staging of
     one host packet.  A chain has ``front``, ``_buffers``, ``process_device`` and ``close``."""
@@ -914,14 +1122,32 @@ class _BankChain(_Chain):
     demodulator slot is held, so slot k's audio is that of a demodulator fed the always-running
     front end's output on its open packets only.  With a squelch, ``process_device`` returns
     after the front end of this call has finished -- the one wait, for the K sums; the
-    demodulators stay asynchronous."""
+    demodulators stay asynchronous.
+
+    ``afc`` (the chains that can tune: ``ReceiverBank``, ``TunedReceiverBank``): None (no meter
+    handle, nothing more enqueued), True, or a dict of ``AfcRule``'s keywords; ``limit_hz`` defaults
+    per slot to half the mode's default width -- beyond that the carrier has left the user filter.
+    The chain then owns a ``FrequencyMeterBank`` (``meter``) and an ``AfcRule``.  Per call, after the
+    front end: the meter is enqueued on the front end's rows, the squelch waits as before, the
+    meter's sums are collected (behind a squelch they have arrived: same stream, enqueued earlier),
+    the rule is stepped, and the demodulators follow.  A slot is active in the rule only in AM, NFM
+    or WFM (SSB has no carrier, CW sits off centre by design) and, with a squelch, only on calls
+    where its gate is open.  The chain remembers the frequencies of ``set_frequencies`` as nominal
+    and, for the slots the rule reports, retunes the front end to nominal + correction through the
+    setters ``set_frequencies`` itself uses, whole Hz, from the next call on, and drops those slots'
+    carried samples.  A user ``set_frequencies`` resets the rule; until the first one nothing is
+    metered.  AFC is the meter and those setter calls: the audio equals a chain without AFC that
+    is given the same ``set_frequencies`` calls between the same packets."""
 
     squelch = None
+    _afc = None                # the AfcRule; the meter handle is self.meter, present only with AFC
+    _nominal = None            # (frequency, [channel frequencies]) of the user's set_frequencies
 
     def __init__(self, input_format: str, sample_rate: int, modes, rate: int, device: int, *front_args,
-                 squelch=None):
+                 squelch=None, afc=None):
         import torch
 
+        rule, self._afc_default_limit = _afc_rule(afc, modes, rate)
         self._torch = torch
         self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
         self._tdev = torch.device("cuda", device)
@@ -940,6 +1166,10 @@ class _BankChain(_Chain):
                         raise ValueError(f"{self._n_channels} squelch thresholds expected, got {len(thresholds)}")
                     for k, thr in enumerate(thresholds):
                         self.squelch.set(k, thr)
+            if rule is not None:
+                self.meter = FrequencyMeterBank(self._n_channels, device)
+                self._afc = rule
+                self._afc_ok = np.array([_mode_id(m) in _AFC_MODE_IDS for m in modes])
             self.set_stream(None)
         except Exception:
             self.close()
@@ -978,6 +1208,41 @@ class _BankChain(_Chain):
         """The last call's gate per slot (bool[K]); None without a squelch."""
         return None if self.squelch is None else self.squelch._open.astype(bool)
 
+    @property
+    def frequency_errors(self):
+        """Every slot's last error estimate in Hz, relative to where it was tuned then (float64[K],
+        NaN before a slot's first); None without AFC."""
+        return None if self._afc is None else self._afc.errors_hz
+
+    @property
+    def corrections(self):
+        """The correction applied to every slot in Hz (float64[K]); None without AFC."""
+        return None if self._afc is None else self._afc.corrections
+
+    def _set_nominal(self, frequency: int, channel_frequencies) -> None:
+        """After a user's ``set_frequencies`` went through: the rule starts again from these."""
+        if self._afc is not None:
+            self._nominal = (int(frequency), [int(f) for f in channel_frequencies])
+            self._afc.reset()
+            self.meter.break_()
+
+    def _step_afc(self, active) -> None:
+        """Collect the meter's sums, step the rule, retune the slots it reports."""
+        m = self.meter
+        m._call("collect", *m._out())
+        rule = self._afc
+        before = rule._estimate.copy(), rule._applied.copy()
+        changed = rule.update(m._re, m._im, active)
+        if changed:
+            frequency, nominal = self._nominal
+            try:
+                self._tune(frequency, [f + int(round(c)) for f, c in zip(nominal, rule._applied)])
+            except Exception:
+                rule._estimate[:], rule._applied[:] = before      # the setters are all or nothing: so is the rule
+                raise
+            for k in changed:
+                m.break_(k)
+
     def mode(self, k: int) -> int:
         return self.demods.mode(k)
 
@@ -987,6 +1252,10 @@ class _BankChain(_Chain):
             raise ValueError(f"mode {mode!r} has quadrature rate {mode_info(mode)[0]}, the bank runs at "
                              f"{self.quadrature_rate}")
         self.demods.set_mode(k, mode)
+        if self._afc is not None:
+            self._afc_ok[k] = _mode_id(mode) in _AFC_MODE_IDS
+            if self._afc_default_limit:
+                self._afc.limit_hz[k] = mode_info(mode)[3] / 2
 
     def set_stream(self, stream_ptr: int | None) -> None:
         """Enqueue every stage on exactly this hipStream_t (None: the demodulator bank's own)."""
@@ -994,6 +1263,8 @@ class _BankChain(_Chain):
         self.front.set_stream(self.demods.stream)
         if self.squelch is not None:
             self.squelch.set_stream(self.demods.stream)
+        if self._afc is not None:
+            self.meter.set_stream(self.demods.stream)
 
     def synchronize(self) -> None:
         self.demods.synchronize()
@@ -1016,6 +1287,9 @@ class _BankChain(_Chain):
         the class); returns every slot's audio sample count, 0 for a slot whose gate is closed."""
         cap = self._buffers(0, n_samples)
         nq = self.front.process_device(raw_ptr, n_samples, self._re.data_ptr(), self._im.data_ptr(), cap)
+        metered = self._nominal is not None
+        if metered:
+            self.meter._call("process", self._re.data_ptr(), self._im.data_ptr(), cap, nq)
         if self.squelch is not None:
             sq = self.squelch
             sq._call("process", self._re.data_ptr(), self._im.data_ptr(), cap, nq, sq._levels.ctypes.data,
@@ -1024,6 +1298,10 @@ class _BankChain(_Chain):
             for k in np.flatnonzero(closed != self._held):
                 self.demods.set_hold(int(k), bool(closed[k]))
             self._held = closed
+            if metered:
+                self._step_afc(self._afc_ok & ~closed)
+        elif metered:
+            self._step_afc(self._afc_ok)
         return self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq, self._audio.data_ptr(),
                                           cap)
 
@@ -1040,6 +1318,10 @@ class _BankChain(_Chain):
         if self.squelch is not None:
             self.squelch.close()
             self.squelch = None
+        if self._afc is not None:
+            self.meter.close()
+            del self.meter
+            self._afc = self._nominal = None
         if self.demods is not None:
             self.demods.close()
             self.demods = None
@@ -1053,9 +1335,9 @@ class ReceiverBank(_BankChain):
     same quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``).
     Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
 
-    def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0, *, squelch=None):
+    def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0, *, squelch=None, afc=None):
         self._cap_for = (None, 0)
-        super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch)
+        super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch, afc=afc)
 
     def _make_front(self):
         return FrontEndBank(self.input_format, self.sample_rate, self.quadrature_rate, self.n_channels, self.device,
@@ -1066,8 +1348,12 @@ class ReceiverBank(_BankChain):
             self._cap_for = (n, self.front.max_outputs(n))
         return self._cap_for[1]
 
-    def set_frequencies(self, frequency: int, channel_frequencies) -> None:
+    def _tune(self, frequency: int, channel_frequencies) -> None:
         self.front.set_frequencies(frequency, channel_frequencies)
+
+    def set_frequencies(self, frequency: int, channel_frequencies) -> None:
+        self._tune(frequency, channel_frequencies)
+        self._set_nominal(frequency, channel_frequencies)
 
 
 # ---------------------------------------------------------------- polyphase channelizer
@@ -1385,7 +1671,10 @@ class RasterReceiverBank(_BankChain):
     quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``)."""
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0,
-                 resample: bool = False, *, squelch=None):
+                 resample: bool = False, *, squelch=None, afc=None):
+        if afc is not None and afc is not False:
+            raise ValueError("a RasterReceiverBank cannot tune: its prototype passes one raster channel per slot and "
+                             "leaves no room to move; use a TunedReceiverBank for AFC")
         modes, rate = _common_rate(modes)
         channels = list(range(len(modes))) if channels is None else [int(c) for c in channels]
         if len(channels) != len(modes):
@@ -1427,13 +1716,13 @@ class TunedReceiverBank(_BankChain):
     Until ``set_frequencies`` is called the slots are raster channels 0, 1, ... untuned."""
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, device: int = 0,
-                 resample: bool = False, *, squelch=None, passband_hz: float | None = None):
+                 resample: bool = False, *, squelch=None, passband_hz: float | None = None, afc=None):
         modes, rate = _common_rate(modes)
         if passband_hz is None:
             passband_hz = int(spacing_hz) / 2 + max(mode_info(m)[2] for m in modes)
         self.passband_hz = float(passband_hz)
         self._resample = bool(resample)
-        super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch)
+        super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch, afc=afc)
 
     def _make_front(self, spacing_hz: int):
         front = Channelizer.for_channels(self.input_format, self.sample_rate, spacing_hz, self.quadrature_rate,
@@ -1453,6 +1742,10 @@ class TunedReceiverBank(_BankChain):
     def set_frequencies(self, frequency: int, channel_frequencies) -> None:
         """The source's tuned frequency and one channel frequency per slot, whole Hz, each within the
         stream's +- sample_rate / 2."""
+        self._tune(frequency, channel_frequencies)
+        self._set_nominal(frequency, channel_frequencies)
+
+    def _tune(self, frequency: int, channel_frequencies) -> None:
         freqs = [int(f) for f in channel_frequencies]
         if len(freqs) != self.n_channels:
             raise ValueError(f"{self.n_channels} channel frequencies expected, got {len(freqs)}")
