@@ -5,7 +5,8 @@ Float = numpy float32 scalars, Int), what the draw thread does with the
 waterfall ring before drawing (paths relative to app/src/main/java/com/mantz_it/rfanalyzer/):
 
 * ``AnalyzerSurface.drawPreprocessing`` (ui/AnalyzerSurface.kt:599-743): viewport
-  start / end bins and pixels (:650-672), per pixel the mean of its bins summed in
+  start / end bins and pixels (:650-672), the drawn pixel range with Kotlin's wrapping Int
+  bounds (:694), per pixel the mean of its bins summed in
   bin order (:693-705), the colour-map index truncated and clamped (:721-722),
   black outside the drawn range (:725), the boxcar time average of the newest
   L + 1 rows summed newest first (:710-714) with its path y and autoscale
@@ -42,6 +43,11 @@ def _kdiv(a: int, b: int) -> int:
     """Kotlin Int division (truncates toward zero)."""
     q = abs(a) // abs(b)
     return q if (a >= 0) == (b >= 0) else -q
+
+
+def _wrap_int(x: int) -> int:
+    """A Kotlin Int result: two's complement wraparound to 32 bits."""
+    return (x + 2 ** 31) % 2 ** 32 - 2 ** 31
 
 
 def gqrx_colormap() -> np.ndarray:
@@ -116,9 +122,15 @@ def draw_preprocess(ring: np.ndarray, read_index: int, peaks, frequency: int, sa
     db_diff = max_db - min_db
     db_width = F32(fft_height) / db_diff
     scale = F32(cmap_size) / db_diff
-    first_pixel = 0 if start >= 0 else kotlin_float_to_int(F32(start * -1) / samples_per_px)
-    last_pixel = (kotlin_float_to_int(F32(fft_size - start) / samples_per_px) if end >= fft_size
-                  else kotlin_float_to_int(F32(end - start) / samples_per_px))
+    with np.errstate(divide="ignore", invalid="ignore"):  # samplesPerPx == 0: x / 0 is +-inf or NaN
+        first_pixel = 0 if start >= 0 else kotlin_float_to_int(F32(start * -1) / samples_per_px)
+        last_pixel = (kotlin_float_to_int(F32(fft_size - start) / samples_per_px) if end >= fft_size
+                      else kotlin_float_to_int(F32(end - start) / samples_per_px))
+
+    # :694 `i in (firstPixel + 1)..<lastPixel-1`: Kotlin Int arithmetic wraps.  A viewport narrower
+    # than one bin has samplesPerPx == 0, so firstPixel saturates to Int.MAX_VALUE or lastPixel to
+    # Int.MIN_VALUE (:668,671) and the bound wraps to the other end of the range.
+    lo_pixel, hi_pixel = _wrap_int(first_pixel + 1), _wrap_int(last_pixel - 1)
 
     if colors is None:
         colors = np.zeros((R, width), np.uint32)
@@ -136,7 +148,7 @@ def draw_preprocess(ring: np.ndarray, read_index: int, peaks, frequency: int, sa
                 break     # at most 5 dirty rows beyond the averaged ones per draw
         row = ring[buffer_index]
         for i in range(width):
-            if first_pixel + 1 <= i < last_pixel - 1:
+            if lo_pixel <= i < hi_pixel:
                 avg, peak_avg, counter = F32(0.0), F32(0.0), 0
                 j = kotlin_float_to_int(F32(i) * samples_per_px)
                 hi = F32(i + 1) * samples_per_px

@@ -44,6 +44,15 @@ __device__ __forceinline__ float jmax(float a, float b) {
     return a > b ? a : b;
 }
 
+// `i in (firstPixel + 1)..<lastPixel-1` (AnalyzerSurface.kt:694) in Kotlin's Int arithmetic, which
+// wraps: a viewport narrower than one bin has samplesPerPx == 0, firstPixel saturates to
+// Int.MAX_VALUE or lastPixel to Int.MIN_VALUE (:668,671), and the bound lands at the other end of
+// the range (lastPixel - 1 == Int.MAX_VALUE draws every pixel above firstPixel, from no bins).
+__device__ __forceinline__ bool pixel_drawn(int i, int first_pixel, int last_pixel) {
+    const int lo = (int)((unsigned)first_pixel + 1u), hi = (int)((unsigned)last_pixel - 1u);
+    return i >= lo && i < hi;
+}
+
 // One block row per refreshed ring row (the host picks them as the reference's
 // dirty-row loop does, AnalyzerSurface.kt:678-684); the other rows keep their colours.
 __global__ void __launch_bounds__(256) draw_rows_kernel(DrawLaunch a) {
@@ -55,7 +64,7 @@ __global__ void __launch_bounds__(256) draw_rows_kernel(DrawLaunch a) {
     const float *row = a.ring + (size_t)buffer_index * a.n;
     const int lm = ring_logm(a.ring_logrs, 31 - __clz(a.n));  // ring storage order (ring_pos)
     unsigned *out = a.colors + (size_t)buffer_index * a.width + i;
-    if (i >= a.first_pixel + 1 && i < a.last_pixel - 1) {
+    if (pixel_drawn(i, a.first_pixel, a.last_pixel)) {
         const bool peaks_here = row_number == 0 && a.peaks_y;
         float avg = 0.0f, peak_avg = 0.0f;
         int counter = 0;
@@ -92,7 +101,7 @@ __global__ void __launch_bounds__(1024) draw_finish_kernel(DrawLaunch a) {
     __shared__ float smin[16], smax[16];
     float mn = 10.0f, mx = -100.0f;
     for (int i = threadIdx.x; i < a.width; i += blockDim.x) {
-        if (i >= a.first_pixel + 1 && i < a.last_pixel - 1) {
+        if (pixel_drawn(i, a.first_pixel, a.last_pixel)) {
             float acc = 0.0f;
             for (int r = 0; r <= a.avg_length; r++) acc += a.avg_rows[(size_t)r * a.width + i];
             const float ta = acc / (float)(a.avg_length + 1);

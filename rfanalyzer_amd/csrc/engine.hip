@@ -1598,6 +1598,11 @@ int rfa_set_fft_size(rfa_handle *h, int32_t fft_size) {
     if (h->stream != h->own_stream) nh->stream = h->stream;
     nh->profile = h->profile;
     nh->generation = h->generation + 1;
+    // the draw thread's colour buffer outlives the size change (AnalyzerSurface.kt:620-627: a new one
+    // only for a new width or row count): rows not yet refreshed keep the colours they had
+    std::swap(nh->d_colors, h->d_colors);
+    std::swap(nh->colors_rows, h->colors_rows);
+    std::swap(nh->colors_width, h->colors_width);
     const int pipe_cus = h->pipe_cus;
     std::swap(*h, *nh);
     rfa_destroy(nh);  // the old tables and buffers
