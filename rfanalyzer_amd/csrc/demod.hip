@@ -1116,11 +1116,10 @@ int rfa_demod_bank_process(rfa_demod_bank *b, const float *re, const float *im, 
     if (!b || !n_audio) return RFA_ERR_INVALID;
     const int K = b->K;
     for (int k = 0; k < K; k++) n_audio[k] = 0;
-    if (n_samples > (size_t)1 << 36 || packet_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40 ||
-        audio_stride > (size_t)1 << 40)
+    if (packet_samples > (size_t)1 << 36 || audio_stride > (size_t)1 << 40)
         return stage_fail(b, RFA_ERR_INVALID, "n_samples too large");
-    if (n_samples && (!re || !im)) return stage_fail(b, RFA_ERR_INVALID, "null input");
-    if (K > 1 && channel_stride < n_samples) return stage_fail(b, RFA_ERR_INVALID, "channel_stride below n_samples");
+    int rc = stage_check_rows(b, (size_t)K, re, im, channel_stride, n_samples);
+    if (rc != RFA_OK) return rc;
     bank_plan(b, (long long)n_samples, (long long)packet_samples);
     long long max_npre = 0, max_audio = 0, max_pk = 0;
     bool any_on = false, any_agc = false;
@@ -1139,7 +1138,7 @@ int rfa_demod_bank_process(rfa_demod_bank *b, const float *re, const float *im, 
         return stage_fail(b, RFA_ERR_INVALID, "call too large for one grid");
     if (!any_on) return RFA_OK;
     STAGE_HIP(b, hipSetDevice(b->device));
-    int rc = stage_grow(b, b->d_pre, b->pre_cap, (size_t)K * (size_t)max_npre, "scratch");
+    rc = stage_grow(b, b->d_pre, b->pre_cap, (size_t)K * (size_t)max_npre, "scratch");
     if (rc == RFA_OK) rc = stage_grow(b, b->d_pk, b->pk_cap, (size_t)K * 3 * (size_t)max_pk, "packet scratch");
     if (rc == RFA_OK) rc = bank_rebuild(b);
     if (rc != RFA_OK) return rc;
@@ -1205,27 +1204,20 @@ int rfa_demod_bank_process_host(rfa_demod_bank *b, const float *re, const float 
     if (!b || !n_audio) return RFA_ERR_INVALID;
     const size_t K = (size_t)b->K;
     for (size_t k = 0; k < K; k++) n_audio[k] = 0;
-    if (n_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40 || audio_stride > (size_t)1 << 40)
-        return stage_fail(b, RFA_ERR_INVALID, "n_samples too large");
-    if (n_samples && (!re || !im)) return stage_fail(b, RFA_ERR_INVALID, "null input");
-    if (K > 1 && channel_stride < n_samples) return stage_fail(b, RFA_ERR_INVALID, "channel_stride below n_samples");
+    if (audio_stride > (size_t)1 << 40) return stage_fail(b, RFA_ERR_INVALID, "n_samples too large");
+    int rc = stage_check_rows(b, K, re, im, channel_stride, n_samples);
+    if (rc != RFA_OK) return rc;
     bank_plan(b, (long long)n_samples, (long long)packet_samples);
     size_t max_audio = 0;
     for (size_t k = 0; k < K; k++)
         if (b->slots[k].mode != RFA_DEMOD_OFF) max_audio = std::max(max_audio, (size_t)b->plans[k].n_audio);
     if (max_audio > audio_stride) return stage_fail(b, RFA_ERR_SIZE, "audio_stride too small for a slot");
     if (max_audio > 0 && !audio) return stage_fail(b, RFA_ERR_INVALID, "null output");
-    STAGE_HIP(b, hipSetDevice(b->device));
-    int rc = stage_grow(b, b->d_in, b->d_in_cap, 2 * K * n_samples, "input staging");
+    rc = stage_upload_rows(b, b->d_in, b->d_in_cap, re, im, channel_stride, K, n_samples);
     if (rc == RFA_OK) rc = stage_grow(b, b->d_out, b->d_out_cap, K * max_audio, "output staging");
     if (rc != RFA_OK) return rc;
-    float *d_re = b->d_in, *d_im = b->d_in + K * n_samples;
-    if (n_samples) {
-        const size_t row = n_samples * sizeof(float), pitch = (K > 1 ? channel_stride : n_samples) * sizeof(float);
-        STAGE_HIP(b, hipMemcpy2DAsync(d_re, row, re, pitch, row, K, hipMemcpyHostToDevice, b->stream));
-        STAGE_HIP(b, hipMemcpy2DAsync(d_im, row, im, pitch, row, K, hipMemcpyHostToDevice, b->stream));
-    }
-    rc = rfa_demod_bank_process(b, d_re, d_im, n_samples, n_samples, packet_samples, b->d_out, max_audio, n_audio);
+    rc = rfa_demod_bank_process(b, b->d_in, b->d_in + K * n_samples, n_samples, n_samples, packet_samples, b->d_out,
+                                max_audio, n_audio);
     if (rc != RFA_OK) return rc;
     for (size_t k = 0; k < K; k++)      // a slot's row of the caller's buffer is written up to its own count
         if (n_audio[k])

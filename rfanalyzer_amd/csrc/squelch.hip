@@ -5,18 +5,9 @@
 // (analyzer/Scheduler.kt:52,161-165,237; database/AppStateRepository.kt:318-324), kept per slot.
 // The device sums; the host turns K sums into K levels and steps K counters.
 //
-// Summation plan.  Samples are cut into tiles of kSqTile = 16384: tile j is [j*kSqTile,
-// min(n, (j+1)*kSqTile)).  A workgroup of 256 threads sums one tile: thread t adds the terms at
-// tile_start + t + 256*m, m ascending, into a double; a wave folds its 64 accumulators with
-// wave_reduce (fixed butterfly), the four waves are added in wave order.  Tiles are added in
-// ascending order.  None of this looks at the row's address, the stride or K, and nothing is
-// atomic, so a sum is a function of the row's values and n alone, bit for bit.
-//   n <= kSqTile (RFA_SQUELCH_ONE_LAUNCH_MAX): one launch, grid (K), the tile's sum is the slot's.
-//   n >  kSqTile: squelch_partials_kernel over (tiles, K), then squelch_fold_kernel over (K).
-// A packet of the banks is a few hundred samples per slot and a 2^24-sample call of 32 slots
-// about 671 K, 41 tiles per slot: the threshold keeps every per-packet call at one launch, and a
-// one-workgroup sum of 16384 samples (128 KiB out of L2) stays well below the front end's time
-// for the raw samples that produce them (DESIGN 5.7i has the measured lines).
+// Term.  term[i] = re[i]^2 + im[i]^2 in float -- the two products and their sum each rounded on
+// its own -- then widened: one double component per slot.  No prologue, no epilogue.  How the terms
+// of a row are added, in how many launches, and what the handle owns for it: slot_sum.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -24,96 +15,28 @@
 #include <new>
 #include <vector>
 
-#include "stage_common.h"
-#include "wave.h"
+#include "slot_sum.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kSqThreads = 256;
-constexpr long long kSqTile = RFA_SQUELCH_TILE;
-static_assert(RFA_SQUELCH_ONE_LAUNCH_MAX == RFA_SQUELCH_TILE, "one launch is the one-tile case of the tile sum");
-static_assert(kSqTile % (4 * kSqThreads) == 0, "the unrolled loop covers whole tiles");
-
-// Sum of re^2 + im^2 over [lo, hi) of one row, hi - lo <= kSqTile; the result is valid in thread 0.
-__device__ __forceinline__ double tile_sum(const float *__restrict__ re, const float *__restrict__ im, long long lo,
-                                           long long hi) {
-    __shared__ double wave_sum[kSqThreads / 64];
-    const int t = (int)threadIdx.x;
-    double acc = 0.0;
-    long long i = lo + t;
-    // four independent pairs of loads in flight, added in index order
-    for (; i + 3 * kSqThreads < hi; i += 4 * kSqThreads) {
-        float r[4], q[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            r[u] = re[i + u * kSqThreads];
-            q[u] = im[i + u * kSqThreads];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const float rr = r[u] * r[u], qq = q[u] * q[u];
-            const float term = rr + qq;
-            acc += (double)term;
-        }
+struct PowerTerm {
+    static constexpr int C = 1;
+    struct In {
+        float r, q;
+    };
+    __device__ __forceinline__ In load(const float *__restrict__ re, const float *__restrict__ im, long long i) const {
+        return In{re[i], im[i]};
     }
-    for (; i < hi; i += kSqThreads) {
-        const float r = re[i], q = im[i];
-        const float rr = r * r, qq = q * q;
+    __device__ __forceinline__ void add(double (&acc)[C], In x) const {
+        const float rr = x.r * x.r, qq = x.q * x.q;
         const float term = rr + qq;
-        acc += (double)term;
+        acc[0] += (double)term;
     }
-    const double w = rfa::wave_reduce(acc, [](double a, double b) { return a + b; });
-    if ((t & 63) == 0) wave_sum[t >> 6] = w;
-    __syncthreads();
-    double s = 0.0;
-    if (t == 0) {
-        s = wave_sum[0];
-#pragma unroll
-        for (int v = 1; v < kSqThreads / 64; v++) s += wave_sum[v];
-    }
-    return s;
-}
-
-// grid (K): n <= kSqTile
-__global__ __launch_bounds__(kSqThreads) void squelch_level_kernel(const float *__restrict__ re,
-                                                                    const float *__restrict__ im, size_t stride,
-                                                                    long long n, double *__restrict__ sums) {
-    const size_t k = blockIdx.x;
-    const double s = tile_sum(re + k * stride, im + k * stride, 0, n);
-    if (threadIdx.x == 0) sums[k] = s;
-}
-
-// grid (tiles, K): partials[k * tiles + j]
-__global__ __launch_bounds__(kSqThreads) void squelch_partials_kernel(const float *__restrict__ re,
-                                                                       const float *__restrict__ im, size_t stride,
-                                                                       long long n, double *__restrict__ partials) {
-    const size_t k = blockIdx.y;
-    const long long lo = (long long)blockIdx.x * kSqTile;
-    const long long hi = lo + kSqTile < n ? lo + kSqTile : n;
-    const double s = tile_sum(re + k * stride, im + k * stride, lo, hi);
-    if (threadIdx.x == 0) partials[k * (size_t)gridDim.x + blockIdx.x] = s;
-}
-
-// grid (K), one wave: the slot's tiles in ascending order.  Lanes fetch 64 partials at a time,
-// lane 0 adds them one by one.
-__global__ __launch_bounds__(64) void squelch_fold_kernel(const double *__restrict__ partials, long long tiles,
-                                                          double *__restrict__ sums) {
-    const size_t k = blockIdx.x;
-    const double *p = partials + k * (size_t)tiles;
-    const int lane = (int)threadIdx.x;
-    double s = 0.0;
-    for (long long base = 0; base < tiles; base += 64) {
-        const double mine = base + lane < tiles ? p[base + lane] : 0.0;
-        const int cnt = tiles - base < 64 ? (int)(tiles - base) : 64;
-        for (int j = 0; j < cnt; j++) {
-            const double v = rfa::readlane_t(mine, j);
-            s = (base == 0 && j == 0) ? v : s + v;
-        }
-    }
-    if (lane == 0) sums[k] = s;
-}
+    __device__ __forceinline__ bool prologue(size_t, const float *, const float *, double (&)[C]) const { return false; }
+    __device__ __forceinline__ void epilogue(size_t, const float *, const float *, long long) const {}
+};
 
 }  // namespace
 
@@ -124,13 +47,7 @@ struct rfa_squelch : StageCore {
     std::vector<float> threshold, level;
     std::vector<int32_t> counter;
     std::vector<double> sums;          // the last call's
-    double *d_sums = nullptr;          // [K]
-    double *h_sums = nullptr;          // pinned, [K]
-    double *d_partials = nullptr;      // [K][tiles] of a call above one tile
-    size_t partials_cap = 0;
-    hipEvent_t copied = nullptr;       // behind the copy of the sums: what a call waits for
-    float *d_in = nullptr;             // staging of the _host entry
-    size_t d_in_cap = 0;
+    SlotSums dev;                      // [K]
 };
 
 namespace {
@@ -186,10 +103,7 @@ int rfa_squelch_create(int device, int32_t n_channels, rfa_squelch **out) {
     s->counter.assign(K, 0);
     s->sums.assign(K, 0.0);
     rc = stage_open(s, device);
-    if (rc == RFA_OK && (hipMalloc(&s->d_sums, K * sizeof(double)) != hipSuccess ||
-                         hipHostMalloc(&s->h_sums, K * sizeof(double), hipHostMallocDefault) != hipSuccess))
-        rc = RFA_ERR_NOMEM;
-    if (rc == RFA_OK && hipEventCreateWithFlags(&s->copied, hipEventDisableTiming) != hipSuccess) rc = RFA_ERR_HIP;
+    if (rc == RFA_OK) rc = slot_sums_open(s->dev, K * PowerTerm::C);
     if (rc != RFA_OK) {
         rfa_squelch_destroy(s);
         return rc;
@@ -201,11 +115,7 @@ int rfa_squelch_create(int device, int32_t n_channels, rfa_squelch **out) {
 int rfa_squelch_destroy(rfa_squelch *s) {
     if (!s) return RFA_ERR_INVALID;
     stage_close_stream(s);
-    if (s->d_sums) (void)hipFree(s->d_sums);
-    if (s->d_partials) (void)hipFree(s->d_partials);
-    if (s->d_in) (void)hipFree(s->d_in);
-    if (s->h_sums) (void)hipHostFree(s->h_sums);
-    if (s->copied) (void)hipEventDestroy(s->copied);
+    slot_sums_close(s->dev);
     delete s;
     return RFA_OK;
 }
@@ -262,56 +172,29 @@ int rfa_squelch_reset(rfa_squelch *s) {
 int rfa_squelch_process(rfa_squelch *s, const float *re, const float *im, size_t channel_stride, size_t n_samples,
                         float *level_db, uint8_t *open) {
     if (!s) return RFA_ERR_INVALID;
-    if (n_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40)
-        return stage_fail(s, RFA_ERR_INVALID, "n_samples too large");
-    if (n_samples && (!re || !im)) return stage_fail(s, RFA_ERR_INVALID, "null input");
-    if (s->K > 1 && channel_stride < n_samples) return stage_fail(s, RFA_ERR_INVALID, "channel_stride below n_samples");
+    int rc = stage_check_rows(s, (size_t)s->K, re, im, channel_stride, n_samples);
+    if (rc != RFA_OK) return rc;
     if (n_samples == 0) {                                  // nothing measured: the rule still steps
         sq_commit(s, nullptr, 0, level_db, open);
         return RFA_OK;
     }
-    const size_t K = (size_t)s->K;
-    const long long n = (long long)n_samples;
-    STAGE_HIP(s, hipSetDevice(s->device));
-    if (n <= kSqTile) {
-        hipLaunchKernelGGL(squelch_level_kernel, dim3((unsigned)K), dim3(kSqThreads), 0, s->stream, re, im,
-                           channel_stride, n, s->d_sums);
-        STAGE_HIP(s, hipGetLastError());
-    } else {
-        const long long tiles = (n + kSqTile - 1) / kSqTile;           // <= 2^22
-        const int rc = stage_grow(s, s->d_partials, s->partials_cap, K * (size_t)tiles, "partial sums");
-        if (rc != RFA_OK) return rc;
-        hipLaunchKernelGGL(squelch_partials_kernel, dim3((unsigned)tiles, (unsigned)K), dim3(kSqThreads), 0, s->stream,
-                           re, im, channel_stride, n, s->d_partials);
-        STAGE_HIP(s, hipGetLastError());
-        hipLaunchKernelGGL(squelch_fold_kernel, dim3((unsigned)K), dim3(64), 0, s->stream, s->d_partials, tiles,
-                           s->d_sums);
-        STAGE_HIP(s, hipGetLastError());
-    }
-    STAGE_HIP(s, hipMemcpyAsync(s->h_sums, s->d_sums, K * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    STAGE_HIP(s, hipEventRecord(s->copied, s->stream));
-    STAGE_HIP(s, hipEventSynchronize(s->copied));           // this copy, not what else the stream holds
-    sq_commit(s, s->h_sums, n_samples, level_db, open);
+    rc = slot_sums_enqueue(s, s->dev, PowerTerm{}, re, im, channel_stride, n_samples);
+    if (rc != RFA_OK) return rc;
+    STAGE_HIP(s, hipEventSynchronize(s->dev.copied));       // this copy, not what else the stream holds
+    sq_commit(s, s->dev.h_sums, n_samples, level_db, open);
     return RFA_OK;
 }
 
 int rfa_squelch_process_host(rfa_squelch *s, const float *re, const float *im, size_t channel_stride, size_t n_samples,
                              float *level_db, uint8_t *open) {
     if (!s) return RFA_ERR_INVALID;
-    if (n_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40)
-        return stage_fail(s, RFA_ERR_INVALID, "n_samples too large");
-    if (n_samples && (!re || !im)) return stage_fail(s, RFA_ERR_INVALID, "null input");
     const size_t K = (size_t)s->K;
-    if (K > 1 && channel_stride < n_samples) return stage_fail(s, RFA_ERR_INVALID, "channel_stride below n_samples");
-    if (n_samples == 0) return rfa_squelch_process(s, nullptr, nullptr, 0, 0, level_db, open);
-    STAGE_HIP(s, hipSetDevice(s->device));
-    const int rc = stage_grow(s, s->d_in, s->d_in_cap, 2 * K * n_samples, "input staging");
+    int rc = stage_check_rows(s, K, re, im, channel_stride, n_samples);
     if (rc != RFA_OK) return rc;
-    float *d_re = s->d_in, *d_im = s->d_in + K * n_samples;
-    const size_t row = n_samples * sizeof(float), pitch = (K > 1 ? channel_stride : n_samples) * sizeof(float);
-    STAGE_HIP(s, hipMemcpy2DAsync(d_re, row, re, pitch, row, K, hipMemcpyHostToDevice, s->stream));
-    STAGE_HIP(s, hipMemcpy2DAsync(d_im, row, im, pitch, row, K, hipMemcpyHostToDevice, s->stream));
-    return rfa_squelch_process(s, d_re, d_im, n_samples, n_samples, level_db, open);
+    if (n_samples == 0) return rfa_squelch_process(s, nullptr, nullptr, 0, 0, level_db, open);
+    rc = stage_upload_rows(s, s->dev.d_in, s->dev.d_in_cap, re, im, channel_stride, K, n_samples);
+    if (rc != RFA_OK) return rc;
+    return rfa_squelch_process(s, s->dev.d_in, s->dev.d_in + K * n_samples, n_samples, n_samples, level_db, open);
 }
 
 int rfa_squelch_get_state(const rfa_squelch *s, double *sums, float *level_db, int32_t *counter, uint8_t *open) {

@@ -1,9 +1,11 @@
-// stage_common.h -- what the streaming stages (ddc.hip, demod.hip, channelizer.hip) share.
+// stage_common.h -- what the streaming stages (ddc.hip, demod.hip, channelizer.hip) and the slot
+// meters (slot_sum.h) share.
 //
 // Host: the handle core (device, stream, last error) with the entries every stage exports in
 // the same form -- set_stream / get_stream / synchronize / the stream's end in destroy -- the
-// device check and stream creation of the create entries, the growth of a staging buffer and
-// the choice of a kernel template by input format.
+// device check and stream creation of the create entries, the growth of a staging buffer, the
+// checks and the upload of a bank call's planar rows and the choice of a kernel template by
+// input format.
 // Device: the one definition of the raw-sample conversion (IQConverter's lookup tables as
 // arithmetic) and the unfused LDS pair load.  The channelizer is bit-exact against the front
 // end because both convert through raw_to_iq below.
@@ -133,6 +135,30 @@ int stage_grow(H *h, T *&p, size_t &cap, size_t want, const char *what) {
     if (hipMalloc(&p, want * sizeof(std::conditional_t<std::is_void_v<T>, char, T>)) != hipSuccess)
         return stage_fail(h, RFA_ERR_NOMEM, std::string("hipMalloc ") + what);
     cap = want;
+    return RFA_OK;
+}
+
+// The planar input rows of a bank call: K rows of n_samples floats, channel_stride apart.
+template <class H>
+int stage_check_rows(H *h, size_t K, const float *re, const float *im, size_t channel_stride, size_t n_samples) {
+    if (n_samples > (size_t)1 << 36 || channel_stride > (size_t)1 << 40)
+        return stage_fail(h, RFA_ERR_INVALID, "n_samples too large");
+    if (n_samples && (!re || !im)) return stage_fail(h, RFA_ERR_INVALID, "null input");
+    if (K > 1 && channel_stride < n_samples) return stage_fail(h, RFA_ERR_INVALID, "channel_stride below n_samples");
+    return RFA_OK;
+}
+
+// Such rows from host memory into the staging buffer d_in as [2][K][n_samples]: re rows, then im
+// rows, on the handle's stream.
+template <class H>
+int stage_upload_rows(H *h, float *&d_in, size_t &cap, const float *re, const float *im, size_t channel_stride,
+                      size_t K, size_t n_samples) {
+    STAGE_HIP(h, hipSetDevice(h->device));
+    const int rc = stage_grow(h, d_in, cap, 2 * K * n_samples, "input staging");
+    if (rc != RFA_OK || n_samples == 0) return rc;
+    const size_t row = n_samples * sizeof(float), pitch = (K > 1 ? channel_stride : n_samples) * sizeof(float);
+    STAGE_HIP(h, hipMemcpy2DAsync(d_in, row, re, pitch, row, K, hipMemcpyHostToDevice, h->stream));
+    STAGE_HIP(h, hipMemcpy2DAsync(d_in + K * n_samples, row, im, pitch, row, K, hipMemcpyHostToDevice, h->stream));
     return RFA_OK;
 }
 

@@ -17,6 +17,7 @@ import pytest
 import freq_ref
 import pfb_ref
 import pfb_tuning_ref as tref
+import slot_sum_plan as plan
 from oracle import demod as odemod
 from rfanalyzer_amd import _lib
 from rfanalyzer_amd import demod
@@ -157,6 +158,43 @@ def test_sums_do_not_move_with_run_stride_alignment_or_bank_size(bank, n):
         assert (bits(s_re[slot]), bits(s_im[slot])) == (bits(base[0][2]), bits(base[1][2])), (k_count, slot)
         others = np.arange(k_count) != slot
         assert not s_re[others].any() and not s_im[others].any() and (terms == n - 1).all()
+
+
+assert plan.R1_LENGTHS == LENGTHS + plan.LONG
+
+
+def same_as_plan(got, n, carried, what):
+    want_re, want_im = plan.r1_sums(n, carried)
+    np.testing.assert_array_equal(bits(got[0]), bits(want_re), f"{what} re")
+    np.testing.assert_array_equal(bits(got[1]), bits(want_im), f"{what} im")
+    assert list(got[2]) == [n if carried else max(n - 1, 0)] * plan.K, what
+
+
+@pytest.mark.parametrize("n", plan.R1_LENGTHS)
+def test_sums_equal_the_summation_plan_bit_for_bit(bank, n):
+    """The order of every addition (tests/slot_sum_plan.py), on finite rows of which two are enveloped,
+    without a carry and with the previous call's last sample; the long lengths reach the tile fold's
+    second fetch."""
+    fm = bank(plan.K)
+    re, im = plan.pin_rows(n)
+    same_as_plan(fm.process(re, im), n, False, f"n {n}, no carry")
+    same_as_plan(fm.process(re, im), n, n > 0, f"n {n}, carried")
+
+
+def test_sums_of_strided_unaligned_rows_equal_the_summation_plan(bank):
+    import torch
+    n = 40000
+    re, im = plan.pin_rows(n)
+    stride = (n // 4 + 2) * 4                                            # beyond n, and every row starts alike
+    wide_re = torch.zeros((plan.K, stride), dtype=torch.float32, device="cuda")
+    wide_im = torch.zeros_like(wide_re)
+    wide_re[:, 1:n + 1] = dev(re)
+    wide_im[:, 1:n + 1] = dev(im)
+    for k in range(plan.K):
+        assert wide_re[k, 1:].data_ptr() % 16 == 4 and wide_im[k, 1:].data_ptr() % 16 == 4
+    fm = bank(plan.K)
+    same_as_plan(fm.process_tensor(wide_re[:, 1:n + 1], wide_im[:, 1:n + 1]), n, False, "no carry")
+    same_as_plan(fm.process_tensor(wide_re[:, 1:n + 1], wide_im[:, 1:n + 1]), n, True, "carried")
 
 
 def test_1024_slots(bank):

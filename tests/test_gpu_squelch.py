@@ -15,6 +15,7 @@ import functools
 import numpy as np
 import pytest
 
+import slot_sum_plan as plan
 import squelch_ref
 from rfanalyzer_amd import _lib
 from rfanalyzer_amd import demod
@@ -154,6 +155,34 @@ def test_sums_do_not_move_with_run_stride_alignment_or_bank_size(bank, n):
         s = other.state()["sums"]
         assert bits(s[slot:slot + 1])[0] == bits(base[2:3])[0], (k_count, slot)
         assert not s[np.arange(k_count) != slot].any()
+
+
+assert plan.POWER_LENGTHS == LENGTHS + plan.LONG
+
+
+@pytest.mark.parametrize("n", plan.POWER_LENGTHS)
+def test_sums_equal_the_summation_plan_bit_for_bit(bank, n):
+    """The order of every addition (tests/slot_sum_plan.py), on finite rows of which two are enveloped;
+    the long lengths reach the tile fold's second fetch."""
+    sq = bank(plan.K)
+    sq.process(*plan.pin_rows(n))
+    np.testing.assert_array_equal(sq.state()["sums"].view(np.int64), plan.power_sums(n).view(np.int64))
+
+
+def test_sums_of_strided_unaligned_rows_equal_the_summation_plan(bank):
+    import torch
+    n = RAGGED
+    re, im = plan.pin_rows(n)
+    stride = (n // 4 + 2) * 4                                            # beyond n, and every row starts alike
+    wide_re = torch.zeros((plan.K, stride), dtype=torch.float32, device="cuda")
+    wide_im = torch.zeros_like(wide_re)
+    wide_re[:, 1:n + 1] = dev(re)
+    wide_im[:, 1:n + 1] = dev(im)
+    for k in range(plan.K):
+        assert wide_re[k, 1:].data_ptr() % 16 == 4 and wide_im[k, 1:].data_ptr() % 16 == 4
+    sq = bank(plan.K)
+    sq.process_tensor(wide_re[:, 1:n + 1], wide_im[:, 1:n + 1])
+    np.testing.assert_array_equal(sq.state()["sums"].view(np.int64), plan.power_sums(n).view(np.int64))
 
 
 def test_1024_slots(bank):
