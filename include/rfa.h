@@ -36,6 +36,7 @@
  *   (extension) every channel of a uniform raster per call rfa_pfb_*() (polyphase channelizer, below;
  *     rfa_pfb_create_rational: at any source sample rate)
  *   (extension) frequency error of every bank slot         rfa_freq_*() (frequency meter bank, below)
+ *   (extension) CTCSS tone sums of every bank slot's audio rfa_tone_*() (tone meter bank, below)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -1074,6 +1075,89 @@ RFA_API int rfa_freq_process_host(rfa_freq *f, const float *re, const float *im,
 RFA_API int rfa_freq_set_stream(rfa_freq *f, void *stream);
 RFA_API int rfa_freq_get_stream(const rfa_freq *f, void **stream);
 RFA_API int rfa_freq_synchronize(rfa_freq *f);
+
+/* ---------------------------------------------------------------------------
+ * Tone meter bank (extension): what a CTCSS tone squelch reads of every slot's audio
+ *
+ * The sub-audible tone under the voice (CTCSS, 67.0 ... 254.1 Hz, neighbours down to
+ * 2.3 Hz apart) tells the users of a shared channel apart.  The device sums, per slot,
+ * the audio row against up to three probe frequencies; the host turns the sums into a
+ * quality (rfa_tone_quality) and decides (demod.ToneRule).  The reference has one
+ * channel, squelched by hand, and nothing like this.
+ *
+ * Audio at sample_rate Hz (an integer, RFA_TONE_MIN_RATE ... RFA_TONE_MAX_RATE), M =
+ * 10 * sample_rate.  A probe is a frequency in tenths of a hertz, int32 f10, 0 = unused,
+ * else 1 <= f10 < 5 * sample_rate; slot k has three: probe 0 the wanted tone, 1 and 2
+ * guards.  The phasor table W[p] = (cos, sin)(2 pi p / M), p = 0 ... M-1, is filled once
+ * at creation in double by the host's libm (rfa_tone_phasor is the function that fills
+ * it).  Every slot has a sample counter base_k, kept on the host modulo M, 0 at first;
+ * sample i of a call meets, for probe j, W[p], p = (f10_j * (base_k + i)) mod M in 64-bit
+ * integers, and the call advances base_k by the slot's n.  A row cut into calls anywhere
+ * meets the phasors of the row given whole.
+ *
+ * Sums of slot k and one call of n_k samples a[i], RFA_TONE_SUMS doubles:
+ *     [2j]   Sc_j = sum (double)a[i] * W[p_j(i)].cos      j = 0, 1, 2
+ *     [2j+1] Ss_j = sum (double)a[i] * W[p_j(i)].sin
+ *     [6]    P    = sum (double)a[i] * (double)a[i]       (every product exact)
+ *     [7]    S1   = sum (double)a[i]
+ * every product rounded once and not contracted with the addition; the two sums of an
+ * unused probe read +0.0.  A non-finite sample makes its slot's sums non-finite and
+ * touches no other slot.  The additions follow the summation plan of the other meters
+ * (tiles of RFA_TONE_TILE) with the slot's own n_k: a slot's sums are a function of its
+ * values, n_k, its probes and base_k alone, bit for bit.  Every n_k up to RFA_TONE_TILE
+ * is one launch; otherwise a partials launch sized by the largest n_k and a fold launch.
+ * A slot with n_k = 0 gets zero sums; a call whose counts are all 0 launches nothing.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_tone rfa_tone;
+
+#define RFA_TONE_MAX_CHANNELS 1024             /* n_channels above this: RFA_ERR_INVALID */
+#define RFA_TONE_MIN_RATE 8000
+#define RFA_TONE_MAX_RATE 384000
+#define RFA_TONE_PROBES 3
+#define RFA_TONE_SUMS 8                        /* doubles per slot and call */
+#define RFA_TONE_TILE 16384                    /* samples of one workgroup; every n_k up to this: one launch */
+
+/* Host only, no device: W[p] of the table for sample_rate, cos(2 pi p / M) and sin of the same
+ * angle, the angle formed in double as ((2 pi) * p) / M.  RFA_ERR_INVALID for a rate outside
+ * the range, p outside 0 ... M-1 or a NULL pointer. */
+RFA_API int rfa_tone_phasor(int32_t sample_rate, int64_t p, double *c, double *s);
+/* Host only: 2 * (sc^2 + ss^2) / (n * p - s1^2), the share of the row's AC power that is
+ * coherent at the probe (1 for a pure tone at the probe over whole periods).  0 where the
+ * denominator is <= 0, NaN where sc, ss, p or s1 is not finite. */
+RFA_API double rfa_tone_quality(double sc, double ss, double p, double s1, int64_t n);
+
+/* 1 <= n_channels <= RFA_TONE_MAX_CHANNELS and a rate in range; arguments are checked before
+ * the device is looked for.  No slot has a probe at first. */
+RFA_API int rfa_tone_create(int device, int32_t n_channels, int32_t sample_rate, rfa_tone **out);
+RFA_API int rfa_tone_destroy(rfa_tone *t);
+RFA_API const char *rfa_tone_last_error(const rfa_tone *t);
+RFA_API int rfa_tone_get_channels(const rfa_tone *t, int32_t *n_channels, int32_t *sample_rate);
+/* Slot k's probes, f10[RFA_TONE_PROBES], from the next call on; the sample counter stays. */
+RFA_API int rfa_tone_set_probes(rfa_tone *t, int32_t k, const int32_t *f10);
+RFA_API int rfa_tone_get_probes(const rfa_tone *t, int32_t k, int32_t *f10);
+/* Slot k's sample counter (k = -1: every slot's) back to 0.  Host only. */
+RFA_API int rfa_tone_break(rfa_tone *t, int32_t k);
+/* Every counter to 0 and the last results to 0; the probes stay. */
+RFA_API int rfa_tone_reset(rfa_tone *t);
+/* Device rows audio_stride floats apart, host counts n_audio[n_channels] (what
+ * rfa_demod_bank_process returns).  Asynchronous: the call's records (counts, counters,
+ * probes) go through a ring of pinned entries guarded by events, then the launch(es), one
+ * copy of the RFA_TONE_SUMS * n_channels sums into pinned memory and an event, all on the
+ * handle's stream.  A steady-state call allocates nothing and waits for nothing.  A count
+ * above audio_stride where n_channels > 1, or a NULL row or count array with any count
+ * > 0, is RFA_ERR_INVALID; nothing is consumed on an error. */
+RFA_API int rfa_tone_process(rfa_tone *t, const float *audio, size_t audio_stride, const size_t *n_audio);
+/* Waits for the last rfa_tone_process's event alone and hands out that call's sums,
+ * [RFA_TONE_SUMS][n_channels], and counts, [n_channels]; either may be NULL.  Without a
+ * call since the last collect it waits for nothing and repeats the values. */
+RFA_API int rfa_tone_collect(rfa_tone *t, double *sums, int64_t *n);
+/* rfa_tone_process with host rows, then rfa_tone_collect: synchronous. */
+RFA_API int rfa_tone_process_host(rfa_tone *t, const float *audio, size_t audio_stride, const size_t *n_audio,
+                                  double *sums, int64_t *n);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_tone_set_stream(rfa_tone *t, void *stream);
+RFA_API int rfa_tone_get_stream(const rfa_tone *t, void **stream);
+RFA_API int rfa_tone_synchronize(rfa_tone *t);
 
 #ifdef __cplusplus
 }

@@ -316,6 +316,25 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_freq_set_stream": (ctypes.c_int, [_h, _vp]),
         "rfa_freq_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
         "rfa_freq_synchronize": (ctypes.c_int, [_h]),
+        # tone meter bank: probe sums of every slot's audio row (rfanalyzer_amd/csrc/tone.hip)
+        "rfa_tone_phasor": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_double)]),
+        "rfa_tone_quality": (ctypes.c_double, [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_int64]),
+        "rfa_tone_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_tone_destroy": (ctypes.c_int, [_h]),
+        "rfa_tone_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_tone_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_tone_set_probes": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_tone_get_probes": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_tone_break": (ctypes.c_int, [_h, ctypes.c_int32]),
+        "rfa_tone_reset": (ctypes.c_int, [_h]),
+        "rfa_tone_process": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp]),
+        "rfa_tone_collect": (ctypes.c_int, [_h, _vp, _vp]),
+        "rfa_tone_process_host": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+        "rfa_tone_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_tone_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_tone_synchronize": (ctypes.c_int, [_h]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -1,4 +1,4 @@
-// slot_sum.h -- the summation plan of the per-slot meters (squelch.hip, freq.hip), device and host.
+// slot_sum.h -- the summation plan of the per-slot meters (squelch.hip, freq.hip, tone.hip), device and host.
 //
 // A meter sums one term per sample of each of K planar rows into C doubles per slot.  Samples are
 // cut into tiles of kTile = 16384: tile j is [j*kTile, min(n, (j+1)*kTile)).  A workgroup of 256
@@ -153,6 +153,101 @@ __global__ __launch_bounds__(64) void slot_fold_kernel(Term term, const double *
     }
 }
 
+// ---------------------------------------------------------------- device, a count per slot
+//
+// The same plan where slot k has its own n = counts[k] >= 0, read from a device array (tone.hip:
+// the demodulator bank's audio counts).  Tile j of slot k is [j*kTile, min(n_k, (j+1)*kTile)) and is
+// summed by tile_sum itself, so a slot's sums are a function of its values and n_k (and of what its
+// term reads) alone, as above.  A slot with n_k = 0 gets +0.0 sums and runs no hook.  The term
+// passed to these kernels hands out a per-slot view of itself,
+//   struct View; View slot(k) const           what implements the term interface above for slot k,
+// for a term that needs more of its slot than the row (tone.hip: probes and sample index).
+
+// grid (K): every counts[k] <= kSlotTile.  sums[c * K + k].
+template <class Term>
+__global__ __launch_bounds__(kSlotThreads) void slot_counted_sum_kernel(Term term, const float *__restrict__ re,
+                                                                        const float *__restrict__ im, size_t stride,
+                                                                        const long long *__restrict__ counts,
+                                                                        double *__restrict__ sums) {
+    using View = typename Term::View;
+    const size_t k = blockIdx.x;
+    const long long n = counts[k];
+    const float *xr = re + k * stride, *xi = im + k * stride;
+    double s[View::C];
+    if (n > 0) {                                               // the same for the whole workgroup
+        const View view = term.slot(k);
+        tile_sum(view, k, xr, xi, 0, n, s);
+        if (threadIdx.x == 0) view.epilogue(k, xr, xi, n);     // behind tile_sum's barrier
+    } else {
+#pragma unroll
+        for (int c = 0; c < View::C; c++) s[c] = 0.0;
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < View::C; c++) sums[c * gridDim.x + k] = s[c];
+    }
+}
+
+// grid (tiles of the largest count, K): partials[(k * gridDim.x + j) * C + c] for the tiles slot k has
+template <class Term>
+__global__ __launch_bounds__(kSlotThreads) void slot_counted_partials_kernel(Term term, const float *__restrict__ re,
+                                                                             const float *__restrict__ im,
+                                                                             size_t stride,
+                                                                             const long long *__restrict__ counts,
+                                                                             double *__restrict__ partials) {
+    using View = typename Term::View;
+    const size_t k = blockIdx.y;
+    const long long n = counts[k];
+    const long long lo = (long long)blockIdx.x * kSlotTile;
+    if (lo >= n) return;                                       // the whole workgroup: slot k has no such tile
+    const long long hi = lo + kSlotTile < n ? lo + kSlotTile : n;
+    double s[View::C];
+    tile_sum(term.slot(k), k, re + k * stride, im + k * stride, lo, hi, s);
+    if (threadIdx.x == 0) {
+        double *p = partials + (k * (size_t)gridDim.x + blockIdx.x) * View::C;
+#pragma unroll
+        for (int c = 0; c < View::C; c++) p[c] = s[c];
+    }
+}
+
+// grid (K), one wave: slot k's own tiles of the partials' `tiles_max` per slot, folded as slot_fold_kernel does
+template <class Term>
+__global__ __launch_bounds__(64) void slot_counted_fold_kernel(Term term, const double *__restrict__ partials,
+                                                               long long tiles_max, const float *__restrict__ re,
+                                                               const float *__restrict__ im, size_t stride,
+                                                               const long long *__restrict__ counts,
+                                                               double *__restrict__ sums) {
+    using View = typename Term::View;
+    constexpr int C = View::C;
+    const size_t k = blockIdx.x;
+    const long long n = counts[k];
+    const long long tiles = (n + kSlotTile - 1) / kSlotTile;   // <= tiles_max
+    const double *p = partials + k * (size_t)tiles_max * C;
+    const int lane = (int)threadIdx.x;
+    double s[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) s[c] = 0.0;
+    for (long long base = 0; base < tiles; base += 64) {
+        double mine[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) mine[c] = base + lane < tiles ? p[(base + lane) * C + c] : 0.0;
+        const int cnt = tiles - base < 64 ? (int)(tiles - base) : 64;
+        for (int j = 0; j < cnt; j++) {
+            const bool first = base == 0 && j == 0;
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                const double v = rfa::readlane_t(mine[c], j);
+                s[c] = first ? v : s[c] + v;
+            }
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < C; c++) sums[c * gridDim.x + k] = s[c];
+        if (n > 0) term.slot(k).epilogue(k, re + k * stride, im + k * stride, n);
+    }
+}
+
 // ---------------------------------------------------------------- host
 
 // What a meter's handle owns for the plan.
@@ -208,6 +303,36 @@ int slot_sums_enqueue(H *h, SlotSums &m, const Term &term, const float *re, cons
         STAGE_HIP(h, hipGetLastError());
         hipLaunchKernelGGL(slot_fold_kernel<Term>, dim3((unsigned)K), dim3(64), 0, h->stream, term, m.d_partials, tiles,
                            re, im, channel_stride, n, m.d_sums);
+        STAGE_HIP(h, hipGetLastError());
+    }
+    m.launched = true;
+    STAGE_HIP(h, hipMemcpyAsync(m.h_sums, m.d_sums, m.count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    STAGE_HIP(h, hipEventRecord(m.copied, h->stream));
+    return RFA_OK;
+}
+
+// The same with a count per slot: d_counts[K] is on the device once the stream gets here, max_n >= 1
+// is the largest of them.  One launch where max_n <= kSlotTile, else partials sized by max_n and a fold.
+template <class Term, class H>
+int slot_sums_enqueue_counted(H *h, SlotSums &m, const Term &term, const float *re, const float *im,
+                              size_t channel_stride, const long long *d_counts, size_t max_n) {
+    using View = typename Term::View;
+    const size_t K = m.count / View::C;
+    m.launched = false;
+    STAGE_HIP(h, hipSetDevice(h->device));
+    if ((long long)max_n <= kSlotTile) {
+        hipLaunchKernelGGL(slot_counted_sum_kernel<Term>, dim3((unsigned)K), dim3(kSlotThreads), 0, h->stream, term, re,
+                           im, channel_stride, d_counts, m.d_sums);
+        STAGE_HIP(h, hipGetLastError());
+    } else {
+        const long long tiles = ((long long)max_n + kSlotTile - 1) / kSlotTile;      // <= 2^22
+        const int rc = stage_grow(h, m.d_partials, m.partials_cap, m.count * (size_t)tiles, "partial sums");
+        if (rc != RFA_OK) return rc;
+        hipLaunchKernelGGL(slot_counted_partials_kernel<Term>, dim3((unsigned)tiles, (unsigned)K), dim3(kSlotThreads),
+                           0, h->stream, term, re, im, channel_stride, d_counts, m.d_partials);
+        STAGE_HIP(h, hipGetLastError());
+        hipLaunchKernelGGL(slot_counted_fold_kernel<Term>, dim3((unsigned)K), dim3(64), 0, h->stream, term,
+                           m.d_partials, tiles, re, im, channel_stride, d_counts, m.d_sums);
         STAGE_HIP(h, hipGetLastError());
     }
     m.launched = true;

@@ -985,6 +985,264 @@ def _afc_rule(afc, modes, rate: int):
     return AfcRule(len(modes), rate, **kw), default_limit
 
 
+# ---------------------------------------------------------------- CTCSS tone squelch
+
+# The 50 standard CTCSS tones in Hz (TIA-603 and the common extensions); neighbours are 2.3 ... 7.6 Hz apart.
+CTCSS_TONES = (67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9,
+               114.8, 118.8, 123.0, 127.3, 131.8, 136.5, 141.3, 146.2, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9,
+               171.3, 173.8, 177.3, 179.9, 183.5, 186.2, 189.9, 192.8, 196.6, 199.5, 203.5, 206.5, 210.7, 218.1,
+               225.7, 229.1, 233.6, 241.8, 250.3, 254.1)
+TONE_SUMS = 8                    # RFA_TONE_SUMS: Sc0 Ss0 Sc1 Ss1 Sc2 Ss2 P S1
+TONE_PROBES = 3
+
+
+def tone_guards(hz: float) -> tuple[float, float]:
+    """The two guard frequencies of a wanted tone: for a tone of ``CTCSS_TONES`` (to 0.05 Hz) its table
+    neighbours -- what another user of the channel would send -- and for any other tone, or at the
+    table's ends, ``hz * 0.965`` and ``hz * 1.035`` rounded to 0.1 Hz."""
+    hz = float(hz)
+    for i in range(1, len(CTCSS_TONES) - 1):
+        if abs(CTCSS_TONES[i] - hz) <= 0.05:
+            return CTCSS_TONES[i - 1], CTCSS_TONES[i + 1]
+    return round(hz * 0.965 * 10) / 10, round(hz * 1.035 * 10) / 10
+
+
+def tone_quality(sc: float, ss: float, p: float, s1: float, n: int) -> float:
+    """``2 (sc^2 + ss^2) / (n p - s1^2)`` (``rfa_tone_quality``): the share of a row's AC power that is
+    coherent at a probe.  0 where the denominator is <= 0, NaN where a sum is not finite.  Host only."""
+    return float(_lib.lib().rfa_tone_quality(float(sc), float(ss), float(p), float(s1), int(n)))
+
+
+def _tone_probes(hz, rate: int = AUDIO_RATE) -> list[int]:
+    """A wanted tone in Hz (None: no tone) -> its three probes in tenths of a hertz, guards included."""
+    if hz is None:
+        return [0] * TONE_PROBES
+    if isinstance(hz, (bool, str, bytes)) or not isinstance(hz, (int, float, np.integer, np.floating)):
+        raise TypeError("a tone is a frequency in Hz or None")
+    if not math.isfinite(hz):
+        raise ValueError("a tone must be finite")
+    f10 = [int(round(float(f) * 10)) for f in (hz, *tone_guards(hz))]
+    if not all(1 <= f < 5 * rate for f in f10):
+        raise ValueError(f"tone {hz} Hz or a guard of it lies outside 0.1 Hz ... {rate / 2} Hz")
+    return f10
+
+
+def _tone_entries(tone, n_channels: int):
+    """The ``tone=`` keyword of a bank chain -> None or the probes of every slot.  Host only: a wrong
+    keyword raises before any handle is made."""
+    if tone is None:
+        return None
+    if isinstance(tone, (bool, str, bytes, int, float)) or not hasattr(tone, "__iter__"):
+        raise TypeError("tone must be None or one entry per slot (a frequency in Hz or None)")
+    entries = list(tone)
+    if len(entries) != n_channels:
+        raise ValueError(f"{n_channels} tones expected, got {len(entries)}")
+    return [_tone_probes(hz) for hz in entries]
+
+
+class ToneMeterBank(_Handle):
+    """Tone meter for ``n_channels`` slots of audio at ``sample_rate`` (``rfa_tone_*``,
+    ``rfanalyzer_amd/csrc/tone.hip``).  Every slot has up to three probes in tenths of a hertz -- the
+    wanted tone and two guards -- and a call sums its audio row, ``n[k]`` samples, into 8 doubles:
+    ``Sc_j, Ss_j`` (the row against probe j's cosine and sine, phase-continuous over calls through a
+    sample counter per slot that ``break_`` zeroes), ``P`` (power) and ``S1`` (plain sum).  The sums
+    are bit-identical from run to run and for any placement of the rows.  ``process_device`` is
+    asynchronous; ``collect`` waits for its copy of the sums alone."""
+
+    _prefix = "rfa_tone"
+
+    def __init__(self, n_channels: int, sample_rate: int = AUDIO_RATE, device: int = 0):
+        self.n_channels, self.sample_rate = int(n_channels), int(sample_rate)
+        self._create("rfa_tone_create", device, self.n_channels, self.sample_rate)
+        self._sums = np.zeros((TONE_SUMS, self.n_channels), np.float64)
+        self._n = np.zeros(self.n_channels, np.int64)
+
+    def set_probes(self, k: int, f10) -> None:
+        """Slot k's probes in tenths of a hertz, up to three, 0 for an unused one; the counter stays."""
+        f10 = [int(f) for f in f10]
+        if len(f10) > TONE_PROBES:
+            raise ValueError(f"at most {TONE_PROBES} probes")
+        arr = (ctypes.c_int32 * TONE_PROBES)(*f10)
+        self._call("set_probes", int(k), arr)
+
+    def probes(self, k: int) -> list[int]:
+        arr = (ctypes.c_int32 * TONE_PROBES)()
+        self._call("get_probes", int(k), arr)
+        return list(arr)
+
+    def break_(self, k: int | None = None) -> None:
+        """Slot k's sample counter (None: every slot's) back to 0.  Host only."""
+        self._call("break", -1 if k is None else int(k))
+
+    def reset(self) -> None:
+        """Every counter and the last results to 0; the probes stay."""
+        self._call("reset")
+
+    def _count_array(self, counts):
+        if isinstance(counts, ctypes.c_size_t * self.n_channels):
+            return counts
+        counts = [int(c) for c in counts]
+        if len(counts) != self.n_channels or min(counts) < 0:
+            raise ValueError(f"{self.n_channels} counts of zero or more expected")
+        return (ctypes.c_size_t * self.n_channels)(*counts)
+
+    def _result(self):
+        return self._sums.copy(), self._n.copy()
+
+    def process_device(self, audio_ptr: int, audio_stride: int, counts) -> None:
+        """Device rows ``audio_stride`` floats apart, one count per slot (``DemodulatorBank``'s).
+        Enqueues the sums and their copy on the handle's stream and returns; ``collect`` hands them out."""
+        self._call("process", audio_ptr, audio_stride, self._count_array(counts))
+
+    def collect(self):
+        """(sums float64[8, K], n int64[K]) of the last ``process_device``; waits for that call's copy
+        and nothing else."""
+        self._call("collect", self._sums.ctypes.data, self._n.ctypes.data)
+        return self._result()
+
+    def process(self, audio, counts=None):
+        """Host float32 [K, width] rows and one count per slot (default: the width) -> (sums, n)."""
+        audio = np.ascontiguousarray(audio, np.float32)
+        if audio.ndim != 2 or audio.shape[0] != self.n_channels:
+            raise ValueError(f"audio must have shape [{self.n_channels}, n]")
+        counts = self._count_array([audio.shape[1]] * self.n_channels if counts is None else counts)
+        if max(counts) > audio.shape[1]:
+            raise ValueError("a count above the rows' length")
+        self._call("process_host", audio.ctypes.data, audio.shape[1], counts, self._sums.ctypes.data,
+                   self._n.ctypes.data)
+        return self._result()
+
+    def process_tensor(self, audio, counts):
+        """A torch.cuda float32 tensor [K, width] (rows may be slices of a wider tensor) and one count
+        per slot -> (sums, n); on torch's current stream."""
+        self._follow_torch_stream(audio)
+        K = self.n_channels
+        if audio.dim() != 2 or audio.shape[0] != K or str(audio.dtype) != "torch.float32":
+            raise ValueError(f"audio must be float32 of shape [{K}, n]")
+        if audio.shape[1] > 1 and audio.stride(1) != 1:
+            raise ValueError("rows must be contiguous")
+        counts = self._count_array(counts)
+        if max(counts) > audio.shape[1]:
+            raise ValueError("a count above the rows' length")
+        self.process_device(audio.data_ptr(), audio.stride(0) if K > 1 else audio.shape[1], counts)
+        return self.collect()
+
+
+class ToneRule:
+    """Tone squelch for ``n_channels`` slots of audio at ``rate``: what to do with the sums of a
+    ``ToneMeterBank``.  Host arithmetic only, no device.
+
+    Per slot the rule accumulates the eight sums and the sample count.  ``update(sums, n, active)``
+    adds the values of the active slots; a slot that is inactive or has ``n = 0`` is reset
+    (accumulators to 0, gate closed).  Once a slot has accumulated ``n >= window_s * rate`` samples
+    it is evaluated and its accumulators are cleared: ``q`` is ``tone_quality`` of probe 0, and the
+    tone is detected where q is finite, ``q > threshold`` and probe 0's power ``Sc^2 + Ss^2`` exceeds
+    ``guard_ratio`` times that of every used guard.  A detection opens the gate and clears the miss
+    count, a miss increments it, ``hang`` misses in a row close the gate.  A slot whose probe 0 is
+    unused (``set_used``) has no tone squelch: it is never evaluated and reads open.
+
+    ``window_s = 0.5``, ``threshold = 0.01``, ``guard_ratio = 4`` and ``hang = 2`` are parameters
+    chosen by hand on a simulation, not measurements of off-air audio."""
+
+    def __init__(self, n_channels: int, rate: float = AUDIO_RATE, *, window_s: float = 0.5, threshold: float = 0.01,
+                 guard_ratio: float = 4.0, hang: int = 2):
+        K = int(n_channels)
+        if K < 1:
+            raise ValueError("at least one slot")
+        if not (math.isfinite(rate) and rate > 0):
+            raise ValueError("rate must be positive")
+        if not (math.isfinite(window_s) and window_s > 0):
+            raise ValueError("window_s must be positive")
+        if not (math.isfinite(threshold) and threshold >= 0):
+            raise ValueError("threshold must be zero or more")
+        if not (math.isfinite(guard_ratio) and guard_ratio >= 0):
+            raise ValueError("guard_ratio must be zero or more")
+        if int(hang) != hang or hang < 1:
+            raise ValueError("hang must be a whole number of windows, at least 1")
+        self.n_channels, self.rate = K, float(rate)
+        self.window_s, self.threshold, self.guard_ratio, self.hang = (float(window_s), float(threshold),
+                                                                      float(guard_ratio), int(hang))
+        self._acc = np.zeros((TONE_SUMS, K))
+        self._acc_n = np.zeros(K, np.int64)
+        self._gate = np.zeros(K, bool)
+        self._misses = np.zeros(K, np.int64)
+        self._quality = np.full(K, np.nan)
+        self._used = np.ones((K, TONE_PROBES), bool)
+
+    def _slot(self, k: int) -> int:
+        if not 0 <= int(k) < self.n_channels:
+            raise ValueError(f"no slot {k}")
+        return int(k)
+
+    def set_used(self, k: int, used) -> None:
+        """Which of slot k's three probes are in use; the slot starts again (``reset(k)``)."""
+        k = self._slot(k)
+        used = [bool(u) for u in used]
+        if len(used) != TONE_PROBES:
+            raise ValueError(f"{TONE_PROBES} flags expected")
+        self._used[k] = used
+        self.reset(k)
+
+    @property
+    def open(self) -> np.ndarray:
+        """The gate per slot (bool[K]); a slot without a wanted tone reads open."""
+        return self._gate | ~self._used[:, 0]
+
+    @property
+    def quality(self) -> np.ndarray:
+        """Every slot's q of its last evaluated window (float64[K]); NaN before its first."""
+        return self._quality.copy()
+
+    def reset(self, k: int | None = None) -> None:
+        """Slot k (None: every slot): accumulators to 0, gate closed, no quality."""
+        s = slice(None) if k is None else self._slot(k)
+        self._acc[:, s] = 0.0
+        for a, v in ((self._acc_n, 0), (self._gate, False), (self._misses, 0), (self._quality, np.nan)):
+            a[s] = v
+
+    def update(self, sums, n, active=None) -> np.ndarray:
+        """One call's sums [8, K] and counts [K] -> ``open``."""
+        K = self.n_channels
+        sums, n = np.asarray(sums, np.float64), np.asarray(n, np.int64)
+        act = np.ones(K, bool) if active is None else np.asarray(active, bool)
+        if sums.shape != (TONE_SUMS, K) or n.shape != (K,) or act.shape != (K,):
+            raise ValueError(f"[{TONE_SUMS}, {K}] sums, {K} counts and flags expected")
+        # every slot at once -- this runs per packet; only a slot whose window is full takes the loop below
+        live = self._used[:, 0] & act & (n > 0)
+        with np.errstate(all="ignore"):
+            if live.all():
+                self._acc += sums
+                self._acc_n += n
+            else:
+                dead = self._used[:, 0] & ~live
+                self._acc[:, dead] = 0.0
+                for a, v in ((self._acc_n, 0), (self._gate, False), (self._misses, 0), (self._quality, np.nan)):
+                    a[dead] = v
+                self._acc += np.where(live, sums, 0.0)
+                self._acc_n += np.where(live, n, 0)
+        due = live & (self._acc_n >= self.window_s * self.rate)
+        for k in np.flatnonzero(due) if due.any() else ():
+            a = self._acc[:, k].copy()
+            q = tone_quality(a[0], a[1], a[6], a[7], int(self._acc_n[k]))
+            self._acc[:, k] = 0.0
+            self._acc_n[k] = 0
+            self._quality[k] = q
+            with np.errstate(all="ignore"):
+                c0 = a[0] * a[0] + a[1] * a[1]
+                hit = bool(math.isfinite(q) and q > self.threshold)
+                for j in (1, 2):
+                    if hit and self._used[k, j]:
+                        hit = bool(c0 > self.guard_ratio * (a[2 * j] * a[2 * j] + a[2 * j + 1] * a[2 * j + 1]))
+            if hit:
+                self._gate[k] = True
+                self._misses[k] = 0
+            else:
+                self._misses[k] += 1
+                if self._misses[k] >= self.hang:
+                    self._gate[k] = False
+        return self.open
+
+
 class _Chain:
     """What the receiver chains share: the context manager, the audio tensor and the staging of
     one host packet.  A chain has ``front``, ``_buffers``, ``process_device`` and ``close``."""
@@ -1137,17 +1395,30 @@ class _BankChain(_Chain):
     setters ``set_frequencies`` itself uses, whole Hz, from the next call on, and drops those slots'
     carried samples.  A user ``set_frequencies`` resets the rule; until the first one nothing is
     metered.  AFC is the meter and those setter calls: the audio equals a chain without AFC that
-    is given the same ``set_frequencies`` calls between the same packets."""
+    is given the same ``set_frequencies`` calls between the same packets.
+
+    ``tone``: None (no tone meter handle, nothing more enqueued), or one entry per slot: a CTCSS tone
+    in Hz, or None for a slot without tone squelch, which is always tone-open.  The chain then owns
+    a ``ToneMeterBank`` on the audio rows (``tone_meter``) and a ``ToneRule``; a slot's guards are
+    ``tone_guards`` of its tone.  Per call, after the demodulator bank of call j is enqueued: the
+    sums of call j-1 are collected (enqueued before call j's kernels: in steady state nothing is
+    waited for), the rule is stepped -- a slot is active where its count in call j-1 was above 0 --
+    the meter is enqueued on call j's audio rows with call j's counts, and call j's counts are
+    returned with 0 for the slots that have a tone and a closed gate.  The audio rows stay as the
+    demodulators wrote them, the gate lags by one call, and a slot that the carrier squelch reopens
+    starts tone-closed until its first window has passed."""
 
     squelch = None
+    _tone = None               # the ToneRule; the meter handle is self.tone_meter, present only with tone=
     _afc = None                # the AfcRule; the meter handle is self.meter, present only with AFC
     _nominal = None            # (frequency, [channel frequencies]) of the user's set_frequencies
 
     def __init__(self, input_format: str, sample_rate: int, modes, rate: int, device: int, *front_args,
-                 squelch=None, afc=None):
+                 squelch=None, afc=None, tone=None):
         import torch
 
         rule, self._afc_default_limit = _afc_rule(afc, modes, rate)
+        probes = _tone_entries(tone, len(modes))
         self._torch = torch
         self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
         self._tdev = torch.device("cuda", device)
@@ -1170,6 +1441,11 @@ class _BankChain(_Chain):
                 self.meter = FrequencyMeterBank(self._n_channels, device)
                 self._afc = rule
                 self._afc_ok = np.array([_mode_id(m) in _AFC_MODE_IDS for m in modes])
+            if probes is not None:
+                self.tone_meter = ToneMeterBank(self._n_channels, AUDIO_RATE, device)
+                self._tone = ToneRule(self._n_channels, AUDIO_RATE)
+                for k, f10 in enumerate(probes):
+                    self._set_tone_probes(k, f10)
             self.set_stream(None)
         except Exception:
             self.close()
@@ -1219,6 +1495,42 @@ class _BankChain(_Chain):
         """The correction applied to every slot in Hz (float64[K]); None without AFC."""
         return None if self._afc is None else self._afc.corrections
 
+    def _tone_rule(self) -> ToneRule:
+        if self._tone is None:
+            raise ValueError("this chain was built without a tone squelch (tone=None)")
+        return self._tone
+
+    @property
+    def tone_open(self):
+        """The tone gate per slot as of the last call (bool[K]; True for a slot without a tone); None
+        without ``tone=``."""
+        return None if self._tone is None else self._tone.open
+
+    @property
+    def tone_quality(self):
+        """Every slot's quality of its last evaluated window (float64[K], NaN before a slot's first);
+        None without ``tone=``."""
+        return None if self._tone is None else self._tone.quality
+
+    def _set_tone_probes(self, k: int, f10) -> None:
+        self.tone_meter.set_probes(k, f10)
+        self.tone_meter.break_(k)
+        self._tone.set_used(k, [f != 0 for f in f10])
+
+    def set_tone(self, k: int, hz: float | None) -> None:
+        """Slot k's wanted tone in Hz (None: no tone squelch on this slot, always tone-open): sets the
+        probes, starts the slot's sample index again and resets its rule."""
+        self._tone_rule()._slot(k)
+        self._set_tone_probes(int(k), _tone_probes(hz))
+
+    def _step_tone(self, counts, cap: int) -> list[int]:
+        """Collect the previous call's sums, step the rule, enqueue the meter on this call's audio."""
+        m = self.tone_meter
+        m._call("collect", m._sums.ctypes.data, m._n.ctypes.data)
+        gate = self._tone.update(m._sums, m._n)
+        m._call("process", self._audio.data_ptr(), cap, self.demods._counts)
+        return [c if g else 0 for c, g in zip(counts, gate)]
+
     def _set_nominal(self, frequency: int, channel_frequencies) -> None:
         """After a user's ``set_frequencies`` went through: the rule starts again from these."""
         if self._afc is not None:
@@ -1265,6 +1577,8 @@ class _BankChain(_Chain):
             self.squelch.set_stream(self.demods.stream)
         if self._afc is not None:
             self.meter.set_stream(self.demods.stream)
+        if self._tone is not None:
+            self.tone_meter.set_stream(self.demods.stream)
 
     def synchronize(self) -> None:
         self.demods.synchronize()
@@ -1302,8 +1616,9 @@ class _BankChain(_Chain):
                 self._step_afc(self._afc_ok & ~closed)
         elif metered:
             self._step_afc(self._afc_ok)
-        return self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq, self._audio.data_ptr(),
-                                          cap)
+        counts = self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq,
+                                            self._audio.data_ptr(), cap)
+        return counts if self._tone is None else self._step_tone(counts, cap)
 
     def process(self, raw_bytes) -> list[np.ndarray]:
         """One raw input packet (host bytes) -> K float32 audio arrays."""
@@ -1322,6 +1637,10 @@ class _BankChain(_Chain):
             self.meter.close()
             del self.meter
             self._afc = self._nominal = None
+        if self._tone is not None:
+            self.tone_meter.close()
+            del self.tone_meter
+            self._tone = None
         if self.demods is not None:
             self.demods.close()
             self.demods = None
@@ -1335,9 +1654,10 @@ class ReceiverBank(_BankChain):
     same quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``).
     Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
 
-    def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0, *, squelch=None, afc=None):
+    def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0, *, squelch=None, afc=None,
+                 tone=None):
         self._cap_for = (None, 0)
-        super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch, afc=afc)
+        super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch, afc=afc, tone=tone)
 
     def _make_front(self):
         return FrontEndBank(self.input_format, self.sample_rate, self.quadrature_rate, self.n_channels, self.device,
@@ -1671,7 +1991,7 @@ class RasterReceiverBank(_BankChain):
     quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``)."""
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0,
-                 resample: bool = False, *, squelch=None, afc=None):
+                 resample: bool = False, *, squelch=None, afc=None, tone=None):
         if afc is not None and afc is not False:
             raise ValueError("a RasterReceiverBank cannot tune: its prototype passes one raster channel per slot and "
                              "leaves no room to move; use a TunedReceiverBank for AFC")
@@ -1680,7 +2000,8 @@ class RasterReceiverBank(_BankChain):
         if len(channels) != len(modes):
             raise ValueError(f"{len(modes)} channels expected, got {len(channels)}")
         self._resample = bool(resample)
-        super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, channels, squelch=squelch)
+        super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, channels, squelch=squelch,
+                         tone=tone)
 
     def _make_front(self, spacing_hz: int, channels):
         make = Channelizer.for_raster_resampled if self._resample else Channelizer.for_raster
@@ -1716,13 +2037,14 @@ class TunedReceiverBank(_BankChain):
     Until ``set_frequencies`` is called the slots are raster channels 0, 1, ... untuned."""
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, device: int = 0,
-                 resample: bool = False, *, squelch=None, passband_hz: float | None = None, afc=None):
+                 resample: bool = False, *, squelch=None, passband_hz: float | None = None, afc=None, tone=None):
         modes, rate = _common_rate(modes)
         if passband_hz is None:
             passband_hz = int(spacing_hz) / 2 + max(mode_info(m)[2] for m in modes)
         self.passband_hz = float(passband_hz)
         self._resample = bool(resample)
-        super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch, afc=afc)
+        super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch, afc=afc,
+                         tone=tone)
 
     def _make_front(self, spacing_hz: int):
         front = Channelizer.for_channels(self.input_format, self.sample_rate, spacing_hz, self.quadrature_rate,
