@@ -83,6 +83,11 @@ struct rfa_handle {
     bool have_rows = false;  // at least one row pushed since the last reset
     float *d_peaks = nullptr;
     float *d_ema = nullptr;
+    // Peak raise (N = 64 K, 8-bit input): the peaks in the ring row's storage order.
+    // The single-launch state scan leaves it equal to the peaks (shadow_fresh); the main kernel of
+    // the next eligible call raises it with that call's rows and the scan folds it back.
+    float *d_peaks_st = nullptr;
+    bool shadow_fresh = false;
     float4 *d_state_part = nullptr;   // chunked state update: [state_chunks][n]
     int state_chunks = 1;
     int state_fused = 1;              // single-launch chunked scan (A/B builds: RFA_STATE_FUSED=0 two kernels)
@@ -432,6 +437,8 @@ int clear_ring(rfa_handle *h) {
 
 int reset_peaks_ema(rfa_handle *h) {
     if (h->d_peaks) HIPCHK(h, rfa::launch_fill(h->d_peaks, h->n, kPeakFill, h->stream));
+    if (h->d_peaks_st) HIPCHK(h, rfa::launch_fill(h->d_peaks_st, h->n, -INFINITY, h->stream));
+    h->shadow_fresh = false;  // the next call takes the full pass
     if (h->d_ema) HIPCHK(h, rfa::launch_fill(h->d_ema, h->n, -INFINITY, h->stream));
     return RFA_OK;
 }
@@ -753,6 +760,8 @@ int rfa_create(const rfa_config *cfg, rfa_handle **out) {
         if (hipMalloc(&h->d_ring_tmp, bytes) != hipSuccess) return bail(RFA_ERR_NOMEM);
     }
     if (cfg->peak_hold && hipMalloc(&h->d_peaks, n * sizeof(float)) != hipSuccess) return bail(RFA_ERR_NOMEM);
+    if (cfg->peak_hold && h->logn == 16 && hipMalloc(&h->d_peaks_st, n * sizeof(float)) != hipSuccess)
+        return bail(RFA_ERR_NOMEM);
     if (cfg->avg_mode == RFA_AVG_EMA && hipMalloc(&h->d_ema, n * sizeof(float)) != hipSuccess) return bail(RFA_ERR_NOMEM);
     if (h->d_peaks || h->d_ema) {
         // enough (bin, chunk) threads to fill the chip (~2^19) for large batches
@@ -806,6 +815,7 @@ int rfa_destroy(rfa_handle *h) {
     hipFree(h->d_ring);
     hipFree(h->d_ring_tmp);
     hipFree(h->d_peaks);
+    hipFree(h->d_peaks_st);
     hipFree(h->d_ema);
     hipFree(h->d_state_part);
     hipFree(h->d_chan);
@@ -951,6 +961,7 @@ static int apply_ring_resize(rfa_handle *h) {
     h->d_ring_tmp = nt;
     h->ring_rows = rn;
     h->cfg.ring_rows = rn;
+    h->shadow_fresh = false;  // the first call on the new ring takes the full pass
     h->dirty.assign((size_t)rn, 1);  // FftProcessor.kt:193
     h->write_index = 0;
     if (h->read_index >= rn) h->read_index = 0;  // rewritten by the frame that triggered the resize
@@ -1033,6 +1044,20 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
             h->generation++;
         }
     }
+    // Peak raise: the main kernel raises the peaks' shadow with this call's rows,
+    // so the state pass reads only the EMA's live tail.  Eligible: every frame lands in the tiled
+    // ring and nowhere else, the launch reaches the staged two-residue 8-bit kernel (the test of
+    // launch_fft_wide: aligned frames, the engine's own window), serial, and the state pass is the
+    // single-launch scan.  An eligible call raises when the shadow equals the peaks, i.e. the
+    // previous state pass was an eligible call's (not the first since creation, a peak reset, a
+    // retune or a call of another kind): else it takes the full pass, which refreshes the shadow --
+    // against a shadow below the peaks every row value would be an atomic.
+    const bool raise_ok = h->d_peaks_st && h->d_state_part && rows_in_ring && !pipe &&
+                          h->logn == 16 && (fmt == RFA_IN_S8 || fmt == RFA_IN_U8) && window == h->d_window &&
+                          h->variant != 1 && h->diag == 0 && !h->d_stamps && (h->ring_logrs & rfa::kRingTile) &&
+                          h->stage && (((uintptr_t)in | (uintptr_t)stride) & 15) == 0 &&
+                          rfa::state_fused_plan(n, (int)n_frames, h->state_chunks, h->state_fused, nullptr, nullptr);
+    const bool raise = raise_ok && h->shadow_fresh;
     FftLaunch a;
     a.in = (const uint8_t *)in;
     a.frame_stride = (long long)stride;
@@ -1040,6 +1065,7 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
     a.fmt = fmt;
     a.window = window;
     a.rows = state_rows;
+    if (raise) a.peaks_st = h->d_peaks_st;
     if (pipe) a.cus = h->pipe_fft_cus;
     if (h->d_ring) {
         a.ring = h->d_ring;
@@ -1064,6 +1090,9 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
         s.part = h->d_state_part;
         s.max_chunks = h->state_chunks;
         s.fused = h->state_fused;
+        s.first_frame = (int)std::max<long long>(0, (long long)n_frames - rfa::ema_tail_frames(h->cfg.ema_alpha));
+        s.peaks_st = raise_ok ? h->d_peaks_st : nullptr;
+        s.raised = raise;
         s.stream = state_stream;
         if (rows_in_ring) {
             s.rows = h->d_ring;
@@ -1075,6 +1104,7 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
             s.row_stride = n;
         }
         if (need_state) HIPCHK(h, rfa::launch_state(s));
+        if (h->d_peaks) h->shadow_fresh = raise_ok;
         if (need_chan) {
             // means, then (channels wider than 16384 bins) the per-span partial sums
             const int spans = rfa::channel_mean_spans(chan_last - chan_first);

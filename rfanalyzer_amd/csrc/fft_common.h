@@ -589,6 +589,15 @@ __device__ __forceinline__ void buf_store_f32x2(float2 x, rsrc_t rs, int voff, i
 //    holds -0 -- db_unscaled's fma rounds an exact cancellation to +0 -- so a compare is enough.)
 //  * EMA: a non-finite frame makes the average non-finite (avg + alpha (x - avg) does that by
 //    itself), and an average that is not finite is re-seeded by the next frame.
+//  * Two paths take a shorter way that the rule allows.  The 64 K main kernel's peak raise
+//    (fft_wide.hip, PKR) sees only rows of 8-bit frames -- Re^2 + Im^2 finite and >= 0, so finite
+//    or -inf, never NaN -- and compares and raises them with integer atomics on the bits, whose
+//    order is Math.max's; it has no NaN code.  And the single-launch scan's EMA reads only its
+//    live tail: the last T(alpha) frames, T the smallest with (1 - alpha)^T <= 2^-51
+//    (ema_tail_frames, fft_kernels.h), started from the carried average (the frames before them
+//    are read for the peaks alone, and not at all when the main kernel raised the peaks).  A
+//    non-finite frame inside the tail restarts the average as above; one before it has decayed
+//    like any other frame.
 RFA_HD float peak_max(float pk, float x) { return (x > pk || x != x) ? x : pk; }
 RFA_HD bool state_finite(float v) { return fabsf(v) < INFINITY; }  // false for NaN, +inf, -inf
 RFA_HD float ema_step(float em, float x, float al) { return state_finite(em) ? fmaf(al, x - em, em) : x; }

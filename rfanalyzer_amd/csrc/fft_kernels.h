@@ -94,6 +94,12 @@ struct FftLaunch {
     int ring_first = 0;         // first frame that is stored into the ring
     int ring_logrs = 0;         // ring row order (ring_pos); must equal the kernel's residue split or 0
     float2 *complex_out = nullptr;  // ordered unscaled FFT (n_frames * N complex) instead of dB
+    // Peak raise (N = 64 K, staged 8-bit input, tiled ring, no caller rows, every frame into the
+    // ring): the peaks in the ring row's storage order (ring_pos), N floats.  The kernel raises a
+    // position to every row value of the call that is above it, with integer atomics on the
+    // float's bits, and the state pass folds the result into the peaks (StateLaunch::peaks_st,
+    // raised).  Null: off, the kernel without the raise.
+    float *peaks_st = nullptr;
     // kernel B of the large-N pair (fmt == kFmtDif): S = dif_ss column residues per
     // frame; work item u is (frame u / S, residue s = u % S), input z_s at
     // in + (u * M) complex, outputs bins S q + s of an N = S * M frame; its dB rows
@@ -188,9 +194,29 @@ struct StateLaunch {
     float4 *part = nullptr;  // chunk summaries [max_chunks][n] (null: sequential kernel only)
     int max_chunks = 1;
     int fused = 1;           // single-launch chunked scan (RFA_STATE_FUSED=0: partial + combine kernels)
+    // The single-launch scan only (every other state kernel ignores them and reads every frame):
+    // first_frame: the EMA reads the frames from it on -- its live tail, n_frames -
+    //   ema_tail_frames(alpha), or 0; the frames before it are read for the peaks alone, and not
+    //   at all when the main kernel raised them;
+    // peaks_st: the peaks' shadow in the ring row's storage order (FftLaunch::peaks_st), left equal
+    //   to the peaks by the fold;
+    // raised: the main kernel raised the shadow with this call's rows, so the frame loop does no
+    //   peak work and the fold takes peaks = max(peaks, shadow).
+    int first_frame = 0;
+    float *peaks_st = nullptr;
+    bool raised = false;
     hipStream_t stream = nullptr;
 };
 hipError_t launch_state(const StateLaunch &a);
+// T(alpha): the smallest T with (1 - alpha)^T <= 2^-51 (in double).  For dB rows spanning under
+// 1024 dB a weight of 2^-36 already puts the frames left out under 2^-26 dB in exact arithmetic,
+// half an ulp of an average of magnitude 0.25 dB.  In fp32 the tail's run and the whole call's
+// then still differ, by one ulp, in a bin with probability about (first gap / ulp) x weight --
+// the gap shrinks by 1 - alpha a frame on average but lives on the average's grid -- which is up
+// to 2^10 / 2^-25 = 2^35 times the weight: one bin in 2000 to 10000 of rows in [-200, 50] dB at
+// 2^-36 (measured on the CPU, alpha 0.5, 0.1 and 0.05 alike).  2^-51 = 2^-35 / 65536 leaves an
+// expected one bin of a 64 K row in that worst case, and one in 2^27 for such rows.
+int ema_tail_frames(float alpha);
 // The single-launch chunked scan launch_state takes for n_frames rows of n bins (max_chunks
 // summaries, fused on): true with its chunk count and chunk length, else false
 bool state_fused_plan(int n, int n_frames, int max_chunks, int fused, int *chunks, int *chunk_len);

@@ -570,14 +570,22 @@ __global__ void state_combine_kernel(StateLaunch a, int chunks) {
 #ifndef RFA_STATE_LOAD_AUX
 #define RFA_STATE_LOAD_AUX 0  // cache policy of the ring-row loads (A/B: 2 = nt)
 #endif
-template <int CH>
+// The EMA reads the frames from first_frame on (its live tail: launch_state), and the chunks
+// divide those; the result is the same function of the rows whether or not the frames before
+// them are read.  They are read for the peaks alone, a share per chunk thread -- unless RAISED:
+// the main kernel has raised the shadow peaks_st with this call's rows already, so no frame loop
+// does peak work, the frames before first_frame are not read and the fold takes the shadow.
+// Whenever a shadow is given the fold leaves it equal to the peaks (the main kernel compares
+// the next call's rows against it).
+template <int CH, bool RAISED = false>
 __global__ void __launch_bounds__(256) state_fused_kernel(StateLaunch a, int chunk_len) {
     constexpr int TPC = 256 / CH, BPB = 4 * TPC;  // threads per chunk, bins per block
     __shared__ float4 part[CH][BPB];
     const int c = threadIdx.x / TPC, l = threadIdx.x % TPC;
     const int bin = blockIdx.x * BPB + 4 * l;
+    const int tail = a.n_frames - a.first_frame;  // frames read
     {
-        const int f0 = c * chunk_len, f1 = min(a.n_frames, f0 + chunk_len);
+        const int f0 = a.first_frame + c * chunk_len, f1 = min(a.n_frames, f0 + chunk_len);
         const float al = a.ema_alpha, keep = 1.0f - al;
         float pk[4], emi[4], b[4];
         bool nan[4];
@@ -587,26 +595,47 @@ __global__ void __launch_bounds__(256) state_fused_kernel(StateLaunch a, int chu
         auto step = [&](float4 x4) {
             const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
 #pragma unroll
-            for (int k = 0; k < 4; k++) state_step(pk[k], nan[k], emi[k], b[k], xs[k], al);
+            for (int k = 0; k < 4; k++) {
+                if constexpr (RAISED) {
+                    emi[k] = ema_step(emi[k], xs[k], al);
+                    b[k] = fmaf(al, xs[k] - b[k], b[k]);
+                } else {
+                    state_step(pk[k], nan[k], emi[k], b[k], xs[k], al);
+                }
+            }
             am *= keep;
         };
-        if (RFA_STATE_BUF && a.ring_rows > 0 && (long long)a.ring_rows * a.n * 4 < (1ll << 31)) {
-            // ring rows: the chunk's first row once, then one row down per frame with the wrap
-            // (FftProcessor.kt:226-227 writeIndex--), as 32-bit buffer offsets -- not a modulo
-            // and a 64-bit address per frame (four chunks share a wave, so they are per lane)
-            const unsigned rowb = (unsigned)a.n * 4u;
-            const rsrc_t rs = make_rsrc(a.rows, (unsigned)a.ring_rows * rowb);
-            int rr = (a.ring_base - f0) % a.ring_rows;
-            if (rr < 0) rr += a.ring_rows;
+        auto peak_step = [&](float4 x4) {  // a frame before the tail: the peaks alone
+            const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) pk[k] = fmaxf(pk[k], xs[k]), nan[k] |= xs[k] != xs[k];
+        };
+        auto frames = [&](int fa, int fb, auto &&each) {
+            if (RFA_STATE_BUF && a.ring_rows > 0 && (long long)a.ring_rows * a.n * 4 < (1ll << 31)) {
+                // ring rows: the chunk's first row once, then one row down per frame with the wrap
+                // (FftProcessor.kt:226-227 writeIndex--), as 32-bit buffer offsets -- not a modulo
+                // and a 64-bit address per frame (four chunks share a wave, so they are per lane)
+                const unsigned rowb = (unsigned)a.n * 4u;
+                const rsrc_t rs = make_rsrc(a.rows, (unsigned)a.ring_rows * rowb);
+                int rr = (a.ring_base - fa) % a.ring_rows;
+                if (rr < 0) rr += a.ring_rows;
 #pragma unroll RFA_STATE_UNROLL
-            for (int f = f0; f < f1; f++) {
-                step(__builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((unsigned)rr * rowb + (unsigned)bin * 4u), 0, RFA_STATE_LOAD_AUX)));
-                rr = rr == 0 ? a.ring_rows - 1 : rr - 1;
-            }
-        } else {
+                for (int f = fa; f < fb; f++) {
+                    each(__builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((unsigned)rr * rowb + (unsigned)bin * 4u), 0, RFA_STATE_LOAD_AUX)));
+                    rr = rr == 0 ? a.ring_rows - 1 : rr - 1;
+                }
+            } else {
 #pragma unroll 4  // frames in flight per thread (profiles/r02c/state_unroll_ab.txt)
-            for (int f = f0; f < f1; f++) step(*reinterpret_cast<const float4 *>(state_row(a, f) + bin));  // storage positions
+                for (int f = fa; f < fb; f++) each(*reinterpret_cast<const float4 *>(state_row(a, f) + bin));  // storage positions
+            }
+        };
+        if constexpr (!RAISED) {
+            if (a.first_frame > 0 && a.peaks) {
+                const int plen = (a.first_frame + CH - 1) / CH;
+                frames(min(a.first_frame, c * plen), min(a.first_frame, (c + 1) * plen), peak_step);
+            }
         }
+        frames(f0, f1, step);
 #pragma unroll
         for (int k = 0; k < 4; k++) part[c][4 * l + k] = state_summary(pk[k], nan[k], am, b[k], emi[k]);
     }
@@ -616,23 +645,25 @@ __global__ void __launch_bounds__(256) state_fused_kernel(StateLaunch a, int chu
     // 30 chunks of 10, not 32); their unseeded summary must not re-seed a non-finite average.
     // The fold is one wave's dependent chain at the end of every block, so the usual case --
     // every chunk holds a frame -- takes a copy of it without that test.
-    const bool full = (CH - 1) * chunk_len < a.n_frames;
+    const bool full = (CH - 1) * chunk_len < tail;
     for (int i = threadIdx.x; i < BPB; i += 256) {
-        const int gb = ring_bin(blockIdx.x * BPB + i, lr, lm);  // natural bin of storage position
+        const int pos = blockIdx.x * BPB + i, gb = ring_bin(pos, lr, lm);  // natural bin of storage position
         float p = a.peaks ? a.peaks[gb] : 0.f;
         float em = a.ema ? a.ema[gb] : 0.f;
+        if constexpr (RAISED) p = peak_max(p, a.peaks_st[pos]);
         auto fold = [&](auto all) {
 #pragma unroll
             for (int cc = 0; cc < CH; cc++) {
-                const bool any = decltype(all)::value || cc * chunk_len < a.n_frames;
+                const bool any = decltype(all)::value || cc * chunk_len < tail;
                 const float4 q = part[cc][i];
-                p = any ? peak_max(p, q.x) : p;
+                if constexpr (!RAISED) p = peak_max(p, q.x);  // (a chunk without a frame holds -inf)
                 em = !any ? em : (!state_finite(em) || q.y < 0.0f) ? q.w : fmaf(q.y, em, q.z);
             }
         };
         if (full) fold(std::true_type{});
         else fold(std::false_type{});
         if (a.peaks) a.peaks[gb] = p;
+        if (a.peaks && a.peaks_st) a.peaks_st[pos] = p;
         if (a.ema) a.ema[gb] = em;
     }
 }
@@ -648,14 +679,30 @@ bool state_fused_plan(int n, int n_frames, int max_chunks, int fused, int *chunk
     if (c < 8 || !fused) return false;
     const int ch = c >= 32 ? 32 : c >= 16 ? 16 : 8;
     if (n % (1024 / ch)) return false;
-    *chunks = ch;
-    *chunk_len = (n_frames + ch - 1) / ch;
+    if (chunks) *chunks = ch;
+    if (chunk_len) *chunk_len = (n_frames + ch - 1) / ch;
     return true;
+}
+
+int ema_tail_frames(float alpha) {
+    const double keep = 1.0 - (double)alpha, bound = std::ldexp(1.0, -51);
+    if (!(keep > 0.0)) return 1;                     // alpha >= 1 (or NaN): the last frame alone
+    if (!(keep < 1.0)) return 0x7fffffff;            // alpha <= 0: nothing decays
+    const double t0 = std::ceil(std::log(bound) / std::log(keep));
+    if (!(t0 < 1.0e9)) return 0x7fffffff;
+    int t = std::max(1, (int)t0);
+    while (t > 1 && std::pow(keep, t - 1) <= bound) t--;  // log / pow rounding at the boundary
+    while (std::pow(keep, t) > bound) t++;
+    return t;
 }
 
 hipError_t launch_state(const StateLaunch &a) {
     if (a.n_frames <= 0) return hipSuccess;
     const int tpb = 256;
+    // raised peaks are folded by the single-launch scan alone
+    if (a.raised && !(a.peaks && a.peaks_st && state_fused_plan(a.n, a.n_frames, a.max_chunks, a.fused, nullptr, nullptr) &&
+                      a.part && (a.ring_logrs & kRingTile)))
+        return hipErrorInvalidValue;
     if (a.ring_rows > 0 && !(a.ring_logrs & kRingTile) && a.ring_logrs >= 3 && a.ring_logrs <= 5 && !kStateTileOff) {
         // column-order ring (N >= 256 K): tiled sequential update (RFA_STATE_TILE=0: A/B off)
         const int m = a.n >> a.ring_logrs;
@@ -670,9 +717,24 @@ hipError_t launch_state(const StateLaunch &a) {
     int chunks = a.part ? std::min(a.max_chunks, (a.n_frames + 7) / 8) : 1;
     int ch = 0, len = 0;
     if (a.part && state_fused_plan(a.n, a.n_frames, a.max_chunks, a.fused, &ch, &len)) {
-        // single-launch form: CH = 8, 16 or 32 chunks
-        auto k = ch == 32 ? state_fused_kernel<32> : ch == 16 ? state_fused_kernel<16> : state_fused_kernel<8>;
-        hipLaunchKernelGGL(k, dim3(a.n / (1024 / ch)), dim3(256), 0, a.stream, a, len);
+        // single-launch form: CH = 8, 16 or 32 chunks.  The EMA reads its live tail: the chunks
+        // are planned over the frames from first_frame on (eight chunks where the tail is shorter
+        // than the plan's smallest scan), so the average does not depend on whether the frames
+        // before it are read too -- they are for the peaks, unless the main kernel raised them
+        // (with the EMA off a raised call reads no row at all)
+        StateLaunch b = a;
+        b.first_frame = !a.ema ? (a.raised ? a.n_frames : 0) : std::min(std::max(a.first_frame, 0), a.n_frames);
+        if (b.first_frame > 0) {
+            const int tail = a.n_frames - b.first_frame;
+            if (!state_fused_plan(a.n, tail, a.max_chunks, a.fused, &ch, &len)) {
+                if (a.n % 128 == 0) ch = 8, len = std::max(1, (tail + 7) / 8);
+                else b.first_frame = 0;  // (ch, len) of the whole call
+            }
+        }
+        auto k = a.raised ? (ch == 32 ? state_fused_kernel<32, true> : ch == 16 ? state_fused_kernel<16, true>
+                                                                                 : state_fused_kernel<8, true>)
+                          : (ch == 32 ? state_fused_kernel<32> : ch == 16 ? state_fused_kernel<16> : state_fused_kernel<8>);
+        hipLaunchKernelGGL(k, dim3(a.n / (1024 / ch)), dim3(256), 0, a.stream, b, len);
         return hipGetLastError();
     }
     if (chunks > 1) {

@@ -48,6 +48,10 @@ namespace rfa {
 #define RFA_STG_OWN 1  // SPLIT halves staged wave-owned (stage_half_own), no item-start barrier (A/B: 0,
                        // profiles/r06/stage_own_ab.txt)
 #endif
+#ifndef RFA_PKR_WIN_UPFRONT
+#define RFA_PKR_WIN_UPFRONT 4  // ... of the peak-raise kernel, whose epilogue holds the 32 shadow values beside the
+                               // 32 row values: 16 spill (72 B of scratch), 12: 60 B, 8: 20 B, 4: none
+#endif
 #ifndef RFA_WIDE_KR1
 #define RFA_WIDE_KR1 0
 #endif
@@ -280,7 +284,7 @@ __device__ __forceinline__ float2 add_w16(float2 acc, float2 x) {
 // products, a subtraction and two complex multiplies (7).  (f32 input keeps the separate
 // twiddle: its 8-B raw samples and the 16-B window pairs in flight would spill.)
 template <int LOGM, int PT, int RS, int FMT, int R, bool STG = false, bool NOWIN = false, int JS = 0, bool CW = false,
-          int QCH = 0>
+          int QCH = 0, int WUPN = RFA_WIN_UPFRONT>
 __device__ __forceinline__ void prestage(float2 (&v)[PT], const float *window_il, const float2 *wide_tw, rsrc_t in_rs,
                                          int tid, int planar_im, const typename Raw<FMT>::T *lraw = nullptr,
                                          const float4 *cw = nullptr) {
@@ -444,7 +448,7 @@ __device__ __forceinline__ void prestage(float2 (&v)[PT], const float *window_il
     // same mul + fma as below, and the remaining points go through the chunk pipeline (all 32 up
     // front spill: 228 B of scratch)
 #if RFA_WIN_UPFRONT
-    constexpr int KU = RFA_WIN_UPFRONT >= PT ? PT : RFA_WIN_UPFRONT;
+    constexpr int KU = WUPN >= PT ? PT : WUPN;
     constexpr bool WUP = STG && RS == 2 && R == 0 && !NOWIN && !CW && QCH == 0 && PT == 32 && KU % C == 0;
     if constexpr (WUP) {
         int zo;  // opaque zero: the scalar offsets are built here, not hoisted out of the item loop
@@ -576,7 +580,9 @@ __device__ __forceinline__ void stage_half_own(const void *src, float2 *buf) {
 // STG: raw input staged through LDS by LDS-DMA one work item ahead (8/16-bit
 // formats, one sub-FFT per workgroup, frame fits the exchange buffer; the
 // host launches a persistent grid and checks 16-byte alignment).
-template <int LOGM, int PT, int RS, int FMT, bool COMPLEX_OUT, int DIAG = 0, bool STG = false>
+// PKR (peak raise; the staged two-residue 8-bit kernels only): every item raises FftLaunch::peaks_st
+// to its row values where they are higher (raise_peak below).
+template <int LOGM, int PT, int RS, int FMT, bool COMPLEX_OUT, int DIAG = 0, bool STG = false, bool PKR = false>
 #ifndef RFA_WIDE_WPE
 #define RFA_WIDE_WPE 0  // A/B builds: waves per EU the wide kernels are compiled for (0: the launch bound's 4)
 #endif
@@ -731,6 +737,28 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
     // than the frame's LDS-DMA, so only the DMA and older operations are waited for)
     int pending_st = 0;
 
+    // PKR: an item's 32 row values per thread against the same 32 positions of peaks_st (residue
+    // r's block; the addresses of the thread's tile stores), loaded after pass 2 so they are live
+    // in the epilogue only (32 running maxima kept across the items, or the shadow loaded before
+    // pass 2, spill: DESIGN.md §5.1).  A value above the shadow is raised with one no-return
+    // integer atomic on the float's bits: signed max for a value whose sign bit is clear, unsigned
+    // min for one whose sign bit is set -- the order of the bits is the order of Math.max, -0 < +0
+    // included.  A stale cached copy of the shadow is never above the true value, so it costs a
+    // redundant atomic at most.  The values are db_unscaled of an 8-bit frame: Re^2 + Im^2 is
+    // finite and >= 0, so a value is finite or -inf, never NaN (the rule for non-finite rows:
+    // state_step, fft_common.h); a NaN in the shadow (a peak some other path left) compares false
+    // and stays, as Math.max has it.
+    static_assert(!PKR || (SPLIT && DIAG == 0 && PT == 32), "peak raise: the staged 64 K 8-bit kernel");
+    typedef float pk4v __attribute__((ext_vector_type(4)));
+    auto raise_peak = [&](float *dst, float x) {
+        const int bits = __builtin_bit_cast(int, x);
+        if (bits >= 0)
+            (void)__hip_atomic_fetch_max(reinterpret_cast<int *>(dst), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else
+            (void)__hip_atomic_fetch_min(reinterpret_cast<unsigned *>(dst), (unsigned)bits, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+    };
+
 #if RFA_RES_HOIST
     auto body = [&]<int RF>(int u, int unext) {  // RF >= 0: every item of this loop is residue RF
 #else
@@ -826,7 +854,8 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
 #else
                 ((r == Rs ? prestage<LOGM, PT, RS, FMT, Rs, STG, (DIAG & 16) != 0, QST ? QN : JS,
 #endif
-                                     RS == 2 && Rs == 1 && FMT <= 2 && (DIAG & 16) == 0, QCH>(
+                                     RS == 2 && Rs == 1 && FMT <= 2 && (DIAG & 16) == 0, QCH,
+                                     PKR ? RFA_PKR_WIN_UPFRONT : RFA_WIN_UPFRONT>(
                                 v, a.window_il, a.wide_tw, in_rs, tid, planar, lraw, a.window_cw)
                           : void()), ...);
             }(std::make_integer_sequence<int, RS>{});
@@ -869,6 +898,46 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
         }
 
         if (!active) return;
+        if constexpr (PKR) {
+            // ---- epilogue of the peak-raise kernel: the tile stores of the form below (the launch
+            // checks that every frame goes to the tiled ring and that no caller rows are asked for)
+            // and the row values against the shadow, whose loads fly under the dB arithmetic
+            constexpr float db_off = -kDbPerLog2 * (float)(2 * (LOGM + 1));
+            int rr = (a.ring_base - frame) % a.ring_rows;
+            if (rr < 0) rr += a.ring_rows;
+            const int tp = (tid >> 6) * 2048 + (tid & 63) * 4;
+            float *blk = a.peaks_st + (size_t)r * M;
+            const rsrc_t p_rs = make_rsrc(blk, M * 4);
+            const rsrc_t ring_rs = make_rsrc(a.ring + (size_t)rr * n + (size_t)r * M, M * 4);
+            pk4v shadow[PT / 4];
+#pragma unroll
+            for (int j = 0; j < PT / 4; j++)
+                shadow[j] = __builtin_bit_cast(pk4v, __builtin_amdgcn_raw_buffer_load_b128(p_rs, tp * 4, j * 1024, 0));
+            __builtin_amdgcn_sched_barrier(0);
+            float d[PT];
+#pragma unroll
+            for (int j = 0; j < PT / 4; j++) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) d[4 * j + e] = db_unscaled(v[(4 * j + e + 16) & 31], db_off);  // nativedsp.cpp:73-78
+                if constexpr (RFA_RING_SC1) buf_store_f32x4(d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3], ring_rs, tp * 4, j * 1024);
+                else buf_store_f32x4_wb(d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3], ring_rs, tp * 4, j * 1024);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < PT / 4; j++) {
+                const pk4v sh = shadow[j];
+                if (d[4 * j] > sh.x || d[4 * j + 1] > sh.y || d[4 * j + 2] > sh.z || d[4 * j + 3] > sh.w) {  // rare
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (d[4 * j + e] > sh[e]) raise_peak(blk + tp + j * 256 + e, d[4 * j + e]);
+                }
+            }
+            // the item-start wait counts the operations younger than the staged frame from below:
+            // the eight stores (the shadow loads have returned; an atomic more only waits longer)
+            pending_st = PT / 4;
+            stamp(u, 6);
+            return;
+        }
         // ---- epilogue: sub-bin i + t*M/16 (i = tid + TPF*b) is full bin kk = r + RS*(i + t*M/16)
         // (kernel B of the large-N pair: kk = s + S*(...) with the runtime S = dif_ss and
         // s = dif_r; the stride and frame length below are then uniform runtime values)
@@ -1044,10 +1113,15 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
 #endif
 }
 
-template <int LOGM, int PT, int RS, int FMT, bool CO, int DIAG = 0, bool STG = false>
+template <int LOGM, int PT, int RS, int FMT, bool CO, int DIAG = 0, bool STG = false, bool PKR = false>
 static hipError_t launch_wide_one(const FftLaunch &a) {
     using G = WGeo<LOGM, PT>;
-    auto kern = &fft_wide_kernel<LOGM, PT, RS, FMT, CO, DIAG, STG>;
+    auto kern = &fft_wide_kernel<LOGM, PT, RS, FMT, CO, DIAG, STG, PKR>;
+    // peak raise: only the kernel that has it may be asked for it, and only for the stores it
+    // taps (every frame into the tiled ring, no caller rows)
+    if (a.peaks_st && !(PKR && a.ring && (a.ring_logrs & kRingTile) && !a.rows && a.ring_first == 0 &&
+                        a.n_frames <= a.ring_rows))
+        return hipErrorInvalidValue;
     const size_t lds = (size_t)G::LDS_BYTES;
     if (!a.wide_tw) return hipErrorInvalidValue;
     if (RS == 2 && FMT <= 2 && (DIAG & 16) == 0 && !a.window_cw) return hipErrorInvalidValue;  // residue 1's table
@@ -1100,6 +1174,10 @@ static hipError_t wide_by_fmt(const FftLaunch &a) {
         const bool stg = a.stage && ((reinterpret_cast<uintptr_t>(a.in) | (uintptr_t)a.frame_stride) & 15) == 0;
         constexpr bool stg8 = G::SLOTS == 1 && M * RS * 2 <= G::HALFP * 8;
         constexpr bool stg16 = G::SLOTS == 1 && M * RS * 4 <= G::HALFP * 8;
+        if constexpr (stg8 && LOGM == 15 && RS == 2) {
+            if (stg && a.peaks_st && a.fmt == 0) return launch_wide_one<LOGM, PT, RS, 0, false, 0, true, true>(a);
+            if (stg && a.peaks_st && a.fmt == 1) return launch_wide_one<LOGM, PT, RS, 1, false, 0, true, true>(a);
+        }
         if constexpr (stg8) {
             if (stg && a.fmt == 0) return launch_wide_one<LOGM, PT, RS, 0, false, 0, true>(a);
             if (stg && a.fmt == 1) return launch_wide_one<LOGM, PT, RS, 1, false, 0, true>(a);
