@@ -37,6 +37,7 @@
  *     rfa_pfb_create_rational: at any source sample rate)
  *   (extension) frequency error of every bank slot         rfa_freq_*() (frequency meter bank, below)
  *   (extension) CTCSS tone sums of every bank slot's audio rfa_tone_*() (tone meter bank, below)
+ *   (extension) a real FIR on every bank slot's audio      rfa_audio_fir_*() (audio FIR bank, below)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -1158,6 +1159,90 @@ RFA_API int rfa_tone_process_host(rfa_tone *t, const float *audio, size_t audio_
 RFA_API int rfa_tone_set_stream(rfa_tone *t, void *stream);
 RFA_API int rfa_tone_get_stream(const rfa_tone *t, void **stream);
 RFA_API int rfa_tone_synchronize(rfa_tone *t);
+
+/* ---------------------------------------------------------------------------
+ * Audio FIR bank (extension): a real FIR on every bank slot's audio row
+ *
+ * What follows the demodulators: a slot that opens on its CTCSS tone would hand the
+ * listener that tone as a hum under the voice; a high-pass at about 300 Hz removes it
+ * (demod.voice_taps).  The reference filters no audio behind its demodulator; the
+ * arithmetic is that of its real FIR (dsp/FirFilter.kt:121-163), one slot at a time.
+ *
+ * Slot k has its own taps t[0 ... T-1] (0 <= T <= RFA_AUDIO_FIR_MAX_TAPS), its own
+ * history and its own sample count per call.  With n = n_audio[k] inputs x[0 ... n-1]
+ * the call writes n outputs
+ *     y[i] = (((+0.0f + t[0] * x[i]) + t[1] * x[i-1]) + ... + t[T-1] * x[i-T+1])
+ * every product rounded to float32, every sum rounded to float32, in this order,
+ * nothing contracted; x[j], j < 0, is the slot's history.  T = 0 is a pass-through:
+ * the output is the input bit for bit, NaN payloads included, without delay.  A
+ * non-finite input reaches the T outputs it is a term of, in its own slot only.
+ *
+ * History: the slot's last RFA_AUDIO_FIR_MAX_TAPS - 1 inputs, on the device, zeros at
+ * first, whatever its tap count (pass-through included): new taps need no special
+ * case.  A call advances it by the slot's n; a slot with n = 0 keeps it.  A row cut
+ * into calls anywhere gives the outputs of the row given whole, bit for bit.
+ *
+ * One launch per call whatever n_channels: one workgroup per (slot, tile of
+ * RFA_AUDIO_FIR_TILE outputs); the history has two buffers per slot and a call writes
+ * the one it does not read.  A call whose counts are all 0 launches nothing.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_audio_fir rfa_audio_fir;
+
+#define RFA_AUDIO_FIR_MAX_CHANNELS 1024        /* n_channels above this: RFA_ERR_INVALID */
+#define RFA_AUDIO_FIR_MAX_TAPS 4096
+#define RFA_AUDIO_FIR_TILE 2048                /* outputs of one workgroup */
+#define RFA_AUDIO_FIR_NARROW_MAX 512           /* a slot with n up to this takes the narrow path */
+/* rfa_audio_fir_plan: the path a slot takes */
+#define RFA_AUDIO_FIR_PATH_NONE 0              /* n = 0: the slot's workgroups return at once */
+#define RFA_AUDIO_FIR_PATH_COPY 1              /* no taps: bitwise copy */
+#define RFA_AUDIO_FIR_PATH_NARROW 2            /* 2 outputs per thread, 2 taps per step */
+#define RFA_AUDIO_FIR_PATH_WIDE 3              /* 8 outputs per thread, 4 taps per step */
+#define RFA_AUDIO_FIR_PLAN_FIELDS 5            /* tile, lds_bytes, path, outputs per thread, workgroups */
+
+/* Host only, no device: what a call of one slot with num_taps taps and n samples runs:
+ * plan[0] RFA_AUDIO_FIR_TILE, [1] the launch's dynamic LDS bytes, [2] the path, [3] outputs
+ * per thread (0 on NONE and COPY), [4] the slot's workgroups that do work, ceil(n / tile).
+ * RFA_ERR_INVALID for num_taps outside 0 ... RFA_AUDIO_FIR_MAX_TAPS, n above 2^36 or NULL. */
+RFA_API int rfa_audio_fir_plan(int32_t num_taps, size_t n, int32_t *plan);
+/* Host only: where sample j (0 oldest ... RFA_AUDIO_FIR_MAX_TAPS - 2 newest) of a slot's history
+ * comes from after a call of n inputs: *from_input 0 and *index into the history before the
+ * call, or *from_input 1 and *index into the call's inputs.  The kernel's own arithmetic.
+ * RFA_ERR_INVALID for j outside the history, n above 2^36 or a NULL pointer. */
+RFA_API int rfa_audio_fir_history_source(size_t n, int32_t j, int32_t *from_input, size_t *index);
+
+/* 1 <= n_channels <= RFA_AUDIO_FIR_MAX_CHANNELS; arguments are checked before the device
+ * is looked for.  Every slot starts as a pass-through with a zero history. */
+RFA_API int rfa_audio_fir_create(int device, int32_t n_channels, rfa_audio_fir **out);
+RFA_API int rfa_audio_fir_destroy(rfa_audio_fir *f);
+RFA_API const char *rfa_audio_fir_last_error(const rfa_audio_fir *f);
+RFA_API int rfa_audio_fir_get_channels(const rfa_audio_fir *f, int32_t *n_channels);
+/* Slot k's taps from the next call on (num_taps = 0: pass-through; taps may then be NULL); the
+ * history stays.  A non-finite tap is RFA_ERR_INVALID and changes nothing.  The upload is
+ * ordered on the handle's stream behind every call enqueued so far, through one pinned stage:
+ * a set_taps waits until the previous set_taps' upload has been made, so a run of them behind
+ * queued calls drains the stream.  The first one after a call waits for nothing. */
+RFA_API int rfa_audio_fir_set_taps(rfa_audio_fir *f, int32_t k, const float *taps, int32_t num_taps);
+/* *num_taps is slot k's tap count; the taps are copied where capacity holds them (taps may be
+ * NULL with capacity 0 to ask for the count). */
+RFA_API int rfa_audio_fir_get_taps(const rfa_audio_fir *f, int32_t k, float *taps, size_t capacity,
+                                   int32_t *num_taps);
+/* Slot k's history (k = -1: every slot's) to zeros, ordered on the stream; the taps stay. */
+RFA_API int rfa_audio_fir_reset(rfa_audio_fir *f, int32_t k);
+/* Device rows in and out, in_stride / out_stride floats apart, host counts n_audio[n_channels]
+ * (what rfa_demod_bank_process returns).  Asynchronous on the handle's stream: the call's
+ * records (counts, tap counts, history buffers) go through a ring of pinned entries guarded by
+ * events, then one launch.  A steady-state call allocates nothing and waits for nothing.
+ * RFA_ERR_INVALID, nothing consumed: a count above either stride where n_channels > 1, a NULL
+ * row or count array with any count > 0, input and output ranges that overlap. */
+RFA_API int rfa_audio_fir_process(rfa_audio_fir *f, const float *in, size_t in_stride, const size_t *n_audio,
+                                  float *out, size_t out_stride);
+/* rfa_audio_fir_process with host rows: synchronous. */
+RFA_API int rfa_audio_fir_process_host(rfa_audio_fir *f, const float *in, size_t in_stride, const size_t *n_audio,
+                                       float *out, size_t out_stride);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_audio_fir_set_stream(rfa_audio_fir *f, void *stream);
+RFA_API int rfa_audio_fir_get_stream(const rfa_audio_fir *f, void **stream);
+RFA_API int rfa_audio_fir_synchronize(rfa_audio_fir *f);
 
 #ifdef __cplusplus
 }

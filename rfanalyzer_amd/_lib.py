@@ -27,6 +27,12 @@ RFA_ERR_STATE = -7
 
 RFA_PFB_MAX_INTERPOLATION = 64      # include/rfa.h
 RFA_PFB_TUNE_MAX_STEPS = 1 << 20    # include/rfa.h
+RFA_AUDIO_FIR_MAX_CHANNELS = 1024   # include/rfa.h
+RFA_AUDIO_FIR_MAX_TAPS = 4096
+RFA_AUDIO_FIR_TILE = 2048
+RFA_AUDIO_FIR_NARROW_MAX = 512
+RFA_AUDIO_FIR_PATHS = ("none", "copy", "narrow", "wide")    # RFA_AUDIO_FIR_PATH_* in order
+RFA_AUDIO_FIR_PLAN_FIELDS = 5
 
 WINDOWS = {"blackman": 0, "hann": 1, "none": 2}
 FORMATS = {"s8": 0, "u8": 1, "s16": 2, "f32": 3, "f32p": 4}
@@ -335,6 +341,24 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_tone_set_stream": (ctypes.c_int, [_h, _vp]),
         "rfa_tone_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
         "rfa_tone_synchronize": (ctypes.c_int, [_h]),
+        # audio FIR bank: a real FIR per slot on the audio rows (rfanalyzer_amd/csrc/audio_fir.hip)
+        "rfa_audio_fir_plan": (ctypes.c_int, [ctypes.c_int32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_fir_history_source": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_int32,
+                                                        ctypes.POINTER(ctypes.c_int32),
+                                                        ctypes.POINTER(ctypes.c_size_t)]),
+        "rfa_audio_fir_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_audio_fir_destroy": (ctypes.c_int, [_h]),
+        "rfa_audio_fir_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_audio_fir_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_fir_set_taps": (ctypes.c_int, [_h, ctypes.c_int32, _fp, ctypes.c_int32]),
+        "rfa_audio_fir_get_taps": (ctypes.c_int, [_h, ctypes.c_int32, _fp, ctypes.c_size_t,
+                                                  ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_fir_reset": (ctypes.c_int, [_h, ctypes.c_int32]),
+        "rfa_audio_fir_process": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t]),
+        "rfa_audio_fir_process_host": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t]),
+        "rfa_audio_fir_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_audio_fir_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_audio_fir_synchronize": (ctypes.c_int, [_h]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

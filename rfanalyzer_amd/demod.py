@@ -44,10 +44,16 @@ built with ``squelch=`` holds the demodulator slots whose gate is closed.
 the lag-1 autocorrelation of the quadrature rows, summed on the device); ``AfcRule`` is the
 per-slot control rule on the host, and ``ReceiverBank`` / ``TunedReceiverBank`` built with ``afc=``
 retune their slots with the two.  The reference has no counterpart.
+
+``AudioFilterBank`` is a real FIR on every slot's audio row behind the demodulator bank
+(``rfa_audio_fir_*``): taps, history and count per slot, one launch per call; ``voice_taps`` is the
+300 Hz high-pass that takes a CTCSS tone out of the voice, and a bank chain built with
+``audio_filter=`` hands out the filtered rows.  The reference has no counterpart.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -1243,6 +1249,163 @@ class ToneRule:
         return self.open
 
 
+# ---------------------------------------------------------------- audio FIR bank
+
+AUDIO_FIR_MAX_TAPS = _lib.RFA_AUDIO_FIR_MAX_TAPS
+AUDIO_FIR_PLAN_FIELDS = ("tile", "lds_bytes", "path", "outputs_per_thread", "workgroups")   # rfa_audio_fir_plan order
+
+
+@functools.lru_cache(maxsize=8)
+def _voice_design(rate: float, cutoff_hz: float, transition_hz: float, attenuation_db: float) -> np.ndarray:
+    """``voice_taps`` of these arguments, read-only: a chain of 32 "voice" slots designs once."""
+    taps = _design_voice_taps(rate, cutoff_hz, transition_hz, attenuation_db)
+    taps.setflags(write=False)
+    return taps
+
+
+def voice_taps(rate: float = AUDIO_RATE, cutoff_hz: float = 300.0, transition_hz: float = 100.0,
+               attenuation_db: float = 60.0) -> np.ndarray:
+    """The high-pass that takes a CTCSS tone out of the voice: the spectral inversion of the reference's
+    own low-pass design, ``lp = create_low_pass_taps(1.0, rate, cutoff_hz, transition_hz, attenuation_db)``
+    (odd in length by its design), ``hp = -lp`` and ``hp[centre] += 1``, in float32.  1309 taps at the
+    defaults, a delay of 654 samples.  ``ValueError`` where the design is rejected or is longer than
+    ``AUDIO_FIR_MAX_TAPS``.  Host only."""
+    return _voice_design(float(rate), float(cutoff_hz), float(transition_hz), float(attenuation_db)).copy()
+
+
+def _design_voice_taps(rate: float, cutoff_hz: float, transition_hz: float, attenuation_db: float) -> np.ndarray:
+    lp = create_low_pass_taps(1.0, float(rate), float(cutoff_hz), float(transition_hz), float(attenuation_db))
+    if lp is None:
+        raise ValueError("the low-pass design rejected these arguments")
+    if lp.size % 2 == 0:
+        raise ValueError("the low-pass design has no centre tap")
+    if lp.size > AUDIO_FIR_MAX_TAPS:
+        raise ValueError(f"{lp.size} taps, above {AUDIO_FIR_MAX_TAPS}: widen transition_hz")
+    hp = -lp
+    hp[lp.size // 2] += np.float32(1.0)
+    return hp.astype(np.float32)
+
+
+def _audio_filter_taps(entry):
+    """One slot's ``audio_filter`` entry -> None (pass-through) or its float32 taps.  Host only."""
+    if entry is None:
+        return None
+    if isinstance(entry, str):
+        if entry != "voice":
+            raise ValueError(f"audio filter {entry!r}: the one named filter is 'voice'")
+        return _voice_design(float(AUDIO_RATE), 300.0, 100.0, 60.0)
+    if isinstance(entry, (bool, bytes, int, float)) or not hasattr(entry, "__len__"):
+        raise ValueError("an audio filter is None, 'voice' or a 1-D array of taps")
+    try:
+        taps = np.asarray(entry, np.float32)
+    except (TypeError, ValueError) as e:
+        raise ValueError("an audio filter is None, 'voice' or a 1-D array of taps") from e
+    if taps.ndim != 1 or taps.size > AUDIO_FIR_MAX_TAPS or not np.isfinite(taps).all():
+        raise ValueError(f"taps must be 1-D, finite and at most {AUDIO_FIR_MAX_TAPS}")
+    return np.ascontiguousarray(taps) if taps.size else None
+
+
+def _audio_filter_entries(audio_filter, n_channels: int):
+    """The ``audio_filter=`` keyword of a bank chain -> None or every slot's taps (None: pass-through).
+    Host only: a wrong entry count or type raises before any device work."""
+    if audio_filter is None:
+        return None
+    if isinstance(audio_filter, (bool, str, bytes, int, float)) or not hasattr(audio_filter, "__iter__"):
+        raise ValueError("audio_filter must be None or one entry per slot (None, 'voice' or an array of taps)")
+    entries = list(audio_filter)
+    if len(entries) != n_channels:
+        raise ValueError(f"{n_channels} audio filters expected, got {len(entries)}")
+    return [_audio_filter_taps(e) for e in entries]
+
+
+def audio_fir_plan(num_taps: int, n: int) -> dict:
+    """What a call of one slot with ``num_taps`` taps and ``n`` samples runs (``rfa_audio_fir_plan``):
+    ``tile`` (outputs per workgroup), ``lds_bytes``, ``path`` ("none", "copy", "narrow", "wide"),
+    ``outputs_per_thread`` and ``workgroups``.  Host only."""
+    out = (ctypes.c_int32 * _lib.RFA_AUDIO_FIR_PLAN_FIELDS)()
+    _lib.check(_lib.lib().rfa_audio_fir_plan(int(num_taps), int(n), out), "rfa_audio_fir_plan")
+    plan = dict(zip(AUDIO_FIR_PLAN_FIELDS, (int(v) for v in out)))
+    plan["path"] = _lib.RFA_AUDIO_FIR_PATHS[plan["path"]]
+    return plan
+
+
+class AudioFilterBank(_Handle):
+    """A real FIR on each of ``n_channels`` audio rows (``rfa_audio_fir_*``,
+    ``rfanalyzer_amd/csrc/audio_fir.hip``): every slot has its own taps (up to 4096; none: a bitwise
+    pass-through), its own history of the last 4095 inputs on the device and its own count per call.
+    Output i is ``((0 + t[0] x[i]) + t[1] x[i-1]) + ...`` with every product and sum rounded to
+    float32, so a row cut into calls anywhere gives the bits of the row given whole.  One launch per
+    call whatever the slot count; ``process_device`` is asynchronous on the handle's stream."""
+
+    _prefix = "rfa_audio_fir"
+
+    def __init__(self, n_channels: int, device: int = 0):
+        self.n_channels = int(n_channels)
+        self._create("rfa_audio_fir_create", device, self.n_channels)
+
+    def set_taps(self, k: int, taps) -> None:
+        """Slot k's taps from the next call on (None or empty: pass-through); its history stays."""
+        if taps is None:
+            self._call("set_taps", int(k), None, 0)
+            return
+        taps = np.ascontiguousarray(taps, np.float32)
+        if taps.ndim != 1:
+            raise ValueError("taps must be 1-D")
+        self._call("set_taps", int(k), taps.ctypes.data_as(_lib._fp), taps.size)
+
+    def taps(self, k: int) -> np.ndarray:
+        return self._query_floats("get_taps", 1, 1, int(k))[0][0]
+
+    def reset(self, k: int | None = None) -> None:
+        """Slot k's history (None: every slot's) to zeros; the taps stay."""
+        self._call("reset", -1 if k is None else int(k))
+
+    @staticmethod
+    def plan(num_taps: int, n: int) -> dict:
+        return audio_fir_plan(num_taps, n)
+
+    def _count_array(self, counts):
+        if isinstance(counts, ctypes.c_size_t * self.n_channels):
+            return counts
+        counts = [int(c) for c in counts]
+        if len(counts) != self.n_channels or min(counts) < 0:
+            raise ValueError(f"{self.n_channels} counts of zero or more expected")
+        return (ctypes.c_size_t * self.n_channels)(*counts)
+
+    def process_device(self, in_ptr: int, in_stride: int, counts, out_ptr: int, out_stride: int) -> None:
+        """Device rows in and out, strides in floats, one count per slot (``DemodulatorBank``'s).
+        Enqueues on the handle's stream and returns."""
+        self._call("process", in_ptr, in_stride, self._count_array(counts), out_ptr, out_stride)
+
+    def process_tensor(self, audio, counts, out) -> None:
+        """torch.cuda float32 tensors [K, width] in and out (rows may be slices of wider tensors) and one
+        count per slot; on torch's current stream."""
+        self._follow_torch_stream(audio)
+        K = self.n_channels
+        for t in (audio, out):
+            if t.dim() != 2 or t.shape[0] != K or str(t.dtype) != "torch.float32":
+                raise ValueError(f"audio and out must be float32 of shape [{K}, n]")
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("rows must be contiguous")
+        counts = self._count_array(counts)
+        if max(counts) > min(audio.shape[1], out.shape[1]):
+            raise ValueError("a count above the rows' length")
+        self.process_device(audio.data_ptr(), audio.stride(0) if K > 1 else audio.shape[1], counts,
+                            out.data_ptr(), out.stride(0) if K > 1 else out.shape[1])
+
+    def process(self, rows, counts=None) -> list[np.ndarray]:
+        """Host float32 [K, width] rows and one count per slot (default: the width) -> K filtered arrays."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[0] != self.n_channels:
+            raise ValueError(f"rows must have shape [{self.n_channels}, n]")
+        counts = self._count_array([rows.shape[1]] * self.n_channels if counts is None else counts)
+        if max(counts) > rows.shape[1]:
+            raise ValueError("a count above the rows' length")
+        out = np.zeros(rows.shape, np.float32)
+        self._call("process_host", rows.ctypes.data, rows.shape[1], counts, out.ctypes.data, rows.shape[1])
+        return [out[k, :c].copy() for k, c in enumerate(counts)]
+
+
 class _Chain:
     """What the receiver chains share: the context manager, the audio tensor and the staging of
     one host packet.  A chain has ``front``, ``_buffers``, ``process_device`` and ``close``."""
@@ -1406,19 +1569,30 @@ class _BankChain(_Chain):
     the meter is enqueued on call j's audio rows with call j's counts, and call j's counts are
     returned with 0 for the slots that have a tone and a closed gate.  The audio rows stay as the
     demodulators wrote them, the gate lags by one call, and a slot that the carrier squelch reopens
-    starts tone-closed until its first window has passed."""
+    starts tone-closed until its first window has passed.
+
+    ``audio_filter``: None (no filter handle, no second audio buffer, nothing more enqueued), or one
+    entry per slot: None (pass-through), ``"voice"`` (``voice_taps()``) or a 1-D float array of taps.
+    The chain then owns an ``AudioFilterBank`` (``audio_fir``) that runs behind the demodulator bank
+    on every call with the demodulator bank's own counts (``audio_counts``) -- not the tone-gated
+    ones, so a slot's filtered stream is continuous across closed gates -- into a second row tensor,
+    which ``audio_tensor`` and ``process`` then return.  The tone meter keeps reading the
+    demodulators' rows: it needs the tone.  The reported counts stay as without the filter."""
 
     squelch = None
+    _filtered = None           # the filter's rows; the handle is self.audio_fir, present only with audio_filter=
+    _audio_counts = None
     _tone = None               # the ToneRule; the meter handle is self.tone_meter, present only with tone=
     _afc = None                # the AfcRule; the meter handle is self.meter, present only with AFC
     _nominal = None            # (frequency, [channel frequencies]) of the user's set_frequencies
 
     def __init__(self, input_format: str, sample_rate: int, modes, rate: int, device: int, *front_args,
-                 squelch=None, afc=None, tone=None):
+                 squelch=None, afc=None, tone=None, audio_filter=None):
         import torch
 
         rule, self._afc_default_limit = _afc_rule(afc, modes, rate)
         probes = _tone_entries(tone, len(modes))
+        filters = _audio_filter_entries(audio_filter, len(modes))
         self._torch = torch
         self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
         self._tdev = torch.device("cuda", device)
@@ -1446,6 +1620,11 @@ class _BankChain(_Chain):
                 self._tone = ToneRule(self._n_channels, AUDIO_RATE)
                 for k, f10 in enumerate(probes):
                     self._set_tone_probes(k, f10)
+            if filters is not None:
+                self.audio_fir = AudioFilterBank(self._n_channels, device)
+                for k, taps in enumerate(filters):
+                    if taps is not None:
+                        self.audio_fir.set_taps(k, taps)
             self.set_stream(None)
         except Exception:
             self.close()
@@ -1531,6 +1710,29 @@ class _BankChain(_Chain):
         m._call("process", self._audio.data_ptr(), cap, self.demods._counts)
         return [c if g else 0 for c, g in zip(counts, gate)]
 
+    @property
+    def audio_tensor(self):
+        """The rows of the last call: the filter's with ``audio_filter=``, else the demodulators'."""
+        return self._audio if self._filtered is None else self._filtered
+
+    @property
+    def audio_counts(self):
+        """The demodulator bank's counts of the last call, before any tone gate (list[int]; None before
+        the first call): what the rows of ``audio_tensor`` hold."""
+        return None if self._audio_counts is None else list(self._audio_counts)
+
+    def _audio_fir(self) -> AudioFilterBank:
+        if not hasattr(self, "audio_fir"):
+            raise ValueError("this chain was built without an audio filter (audio_filter=None)")
+        return self.audio_fir
+
+    def set_audio_filter(self, k: int, entry) -> None:
+        """Slot k's audio filter from the next call on: None, ``"voice"`` or taps; its history stays."""
+        fir = self._audio_fir()
+        if not 0 <= int(k) < self._n_channels:
+            raise ValueError(f"slot {k} outside 0 ... {self._n_channels - 1}")
+        fir.set_taps(int(k), _audio_filter_taps(entry))
+
     def _set_nominal(self, frequency: int, channel_frequencies) -> None:
         """After a user's ``set_frequencies`` went through: the rule starts again from these."""
         if self._afc is not None:
@@ -1579,6 +1781,8 @@ class _BankChain(_Chain):
             self.meter.set_stream(self.demods.stream)
         if self._tone is not None:
             self.tone_meter.set_stream(self.demods.stream)
+        if hasattr(self, "audio_fir"):
+            self.audio_fir.set_stream(self.demods.stream)
 
     def synchronize(self) -> None:
         self.demods.synchronize()
@@ -1593,6 +1797,8 @@ class _BankChain(_Chain):
             self._re = torch.empty(shape, dtype=torch.float32, device=self._tdev)
             self._im = torch.empty(shape, dtype=torch.float32, device=self._tdev)
             self._audio = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+            if hasattr(self, "audio_fir"):
+                self._filtered = torch.empty(shape, dtype=torch.float32, device=self._tdev)
         return self._re.shape[1]
 
     def process_device(self, raw_ptr: int, n_samples: int) -> list[int]:
@@ -1618,12 +1824,16 @@ class _BankChain(_Chain):
             self._step_afc(self._afc_ok)
         counts = self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq,
                                             self._audio.data_ptr(), cap)
+        self._audio_counts = counts
+        if self._filtered is not None:
+            self.audio_fir._call("process", self._audio.data_ptr(), cap, self.demods._counts,
+                                 self._filtered.data_ptr(), cap)
         return counts if self._tone is None else self._step_tone(counts, cap)
 
     def process(self, raw_bytes) -> list[np.ndarray]:
         """One raw input packet (host bytes) -> K float32 audio arrays."""
         got = self._process_host(raw_bytes, self.demods)
-        audio = self._audio.cpu().numpy()
+        audio = self.audio_tensor.cpu().numpy()
         return [audio[k, :g].copy() for k, g in enumerate(got)]
 
     def close(self) -> None:
@@ -1641,6 +1851,10 @@ class _BankChain(_Chain):
             self.tone_meter.close()
             del self.tone_meter
             self._tone = None
+        if hasattr(self, "audio_fir"):
+            self.audio_fir.close()
+            del self.audio_fir
+            self._filtered = None
         if self.demods is not None:
             self.demods.close()
             self.demods = None
@@ -1655,9 +1869,10 @@ class ReceiverBank(_BankChain):
     Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
 
     def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0, *, squelch=None, afc=None,
-                 tone=None):
+                 tone=None, audio_filter=None):
         self._cap_for = (None, 0)
-        super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch, afc=afc, tone=tone)
+        super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch, afc=afc, tone=tone,
+                         audio_filter=audio_filter)
 
     def _make_front(self):
         return FrontEndBank(self.input_format, self.sample_rate, self.quadrature_rate, self.n_channels, self.device,
@@ -1991,7 +2206,7 @@ class RasterReceiverBank(_BankChain):
     quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``)."""
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0,
-                 resample: bool = False, *, squelch=None, afc=None, tone=None):
+                 resample: bool = False, *, squelch=None, afc=None, tone=None, audio_filter=None):
         if afc is not None and afc is not False:
             raise ValueError("a RasterReceiverBank cannot tune: its prototype passes one raster channel per slot and "
                              "leaves no room to move; use a TunedReceiverBank for AFC")
@@ -2001,7 +2216,7 @@ class RasterReceiverBank(_BankChain):
             raise ValueError(f"{len(modes)} channels expected, got {len(channels)}")
         self._resample = bool(resample)
         super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, channels, squelch=squelch,
-                         tone=tone)
+                         tone=tone, audio_filter=audio_filter)
 
     def _make_front(self, spacing_hz: int, channels):
         make = Channelizer.for_raster_resampled if self._resample else Channelizer.for_raster
@@ -2037,14 +2252,15 @@ class TunedReceiverBank(_BankChain):
     Until ``set_frequencies`` is called the slots are raster channels 0, 1, ... untuned."""
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, device: int = 0,
-                 resample: bool = False, *, squelch=None, passband_hz: float | None = None, afc=None, tone=None):
+                 resample: bool = False, *, squelch=None, passband_hz: float | None = None, afc=None, tone=None,
+                 audio_filter=None):
         modes, rate = _common_rate(modes)
         if passband_hz is None:
             passband_hz = int(spacing_hz) / 2 + max(mode_info(m)[2] for m in modes)
         self.passband_hz = float(passband_hz)
         self._resample = bool(resample)
         super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch, afc=afc,
-                         tone=tone)
+                         tone=tone, audio_filter=audio_filter)
 
     def _make_front(self, spacing_hz: int):
         front = Channelizer.for_channels(self.input_format, self.sample_rate, spacing_hz, self.quadrature_rate,
