@@ -38,6 +38,7 @@
  *   (extension) frequency error of every bank slot         rfa_freq_*() (frequency meter bank, below)
  *   (extension) CTCSS tone sums of every bank slot's audio rfa_tone_*() (tone meter bank, below)
  *   (extension) a real FIR on every bank slot's audio      rfa_audio_fir_*() (audio FIR bank, below)
+ *   (extension) every bank slot's audio to 8 / 16 kHz PCM  rfa_audio_rs_*() (audio resampler bank, below)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -1243,6 +1244,117 @@ RFA_API int rfa_audio_fir_process_host(rfa_audio_fir *f, const float *in, size_t
 RFA_API int rfa_audio_fir_set_stream(rfa_audio_fir *f, void *stream);
 RFA_API int rfa_audio_fir_get_stream(const rfa_audio_fir *f, void **stream);
 RFA_API int rfa_audio_fir_synchronize(rfa_audio_fir *f);
+
+/* ---------------------------------------------------------------------------
+ * Audio resampler bank (extension): every bank slot's audio row to 8 / 16 kHz PCM
+ *
+ * What follows the audio FIR: loggers, codecs and recognisers want narrow-band s16,
+ * not 48 kHz float.  The reference's AudioSink plays float at 48 kHz and resamples
+ * nothing; this stage is defined by the text below and checked against its
+ * restatement in numpy (tests/audio_rs_ref.py), bit for bit.
+ *
+ * Handle constants, one set for all slots, fixed at creation: a ratio L / D with
+ * 1 <= L <= RFA_AUDIO_RS_MAX_L, L <= D <= RFA_AUDIO_RS_MAX_D and gcd(L, D) = 1, and
+ * one real prototype FIR h[0 ... T-1], all finite, T <= RFA_AUDIO_RS_MAX_TAPS, with
+ * J = ceil(T / L) taps per phase, 1 <= J <= RFA_AUDIO_RS_MAX_PHASE_TAPS.  L = D = 1
+ * may have T = 0: no filter, only the conversion.
+ *
+ * Per-slot state: a history of the slot's last RFA_AUDIO_RS_HISTORY inputs on the
+ * device, zeros at first (two buffers, a call writes the one it does not read, as in
+ * the audio FIR bank), and an offset r, 0 <= r < D, on the host, 0 at first: the
+ * position of the slot's next output relative to the next input it will receive, in
+ * ticks of the rate L * f_in.
+ *
+ * A call gives slot k n = n_audio[k] inputs x[0 ... n-1].  Its outputs are
+ * m = 0, 1, ... while r + m * D < n * L.  Output m has u = r + m * D, input index
+ * i = floor(u / L) and phase p = u mod L, and
+ *     y = (((+0.0f + h[p] * x[i]) + h[p+L] * x[i-1]) + ... + h[p+(J-1)L] * x[i-J+1])
+ * Taps at or beyond T count as +0.0f and are still multiplied and added.  Every
+ * product and every sum is rounded to float32 in this order, nothing contracted;
+ * x[j], j < 0, is the history.  After the call r <- r + n_out * D - n * L and the
+ * history advances by n.  A slot with n = 0 does nothing and keeps everything.  So
+ * n_out = ceil((n * L - r) / D) for n * L > r, else 0; a stream cut into calls anywhere
+ * gives the outputs of the stream given whole, bit for bit, with the same total count;
+ * with T = 0, y = x bitwise.
+ *
+ * PCM: v = y * 32768.0f (exact); NaN -> 0; v >= 32767 -> 32767; v <= -32768 -> -32768;
+ * otherwise (int16_t)rintf(v), ties to even.  A PCM value q read back through the
+ * RFA_IN_S16LE conversion is exactly q / 32768.
+ *
+ * One launch per call whatever n_channels: a grid of (output tiles of the longest row,
+ * n_channels) workgroups.  A call whose counts are all 0 launches nothing.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_audio_rs rfa_audio_rs;
+
+#define RFA_AUDIO_RS_MAX_CHANNELS 1024         /* n_channels above this: RFA_ERR_INVALID */
+#define RFA_AUDIO_RS_MAX_L 160
+#define RFA_AUDIO_RS_MAX_D 1024
+#define RFA_AUDIO_RS_MAX_TAPS 16384            /* T */
+#define RFA_AUDIO_RS_MAX_PHASE_TAPS 4096       /* J = ceil(T / L) */
+#define RFA_AUDIO_RS_HISTORY 4095              /* inputs a slot keeps between calls */
+#define RFA_AUDIO_RS_MAX_TILE 1024             /* outputs of one workgroup, at most */
+/* rfa_audio_rs_plan: the path a slot takes */
+#define RFA_AUDIO_RS_PATH_NONE 0               /* n = 0: the slot's workgroups return at once */
+#define RFA_AUDIO_RS_PATH_CONVERT 1            /* T = 0: the conversion alone */
+#define RFA_AUDIO_RS_PATH_DECIMATE 2           /* L = 1: one tap row for all outputs, samples de-interleaved by D */
+#define RFA_AUDIO_RS_PATH_POLYPHASE 3          /* L > 1: every output reads its own phase row */
+#define RFA_AUDIO_RS_PLAN_FIELDS 5             /* tile, lds_bytes, path, outputs per thread, workgroups */
+
+/* Host only, no device: the call rule, the kernel launch's own arithmetic.  A slot at offset r
+ * given n inputs writes *n_out outputs and is then at offset *r_next.  No overflow for n up to
+ * 2^36.  RFA_ERR_INVALID for a ratio outside the limits above, r outside 0 ... D-1, n above
+ * 2^36 or a NULL pointer. */
+RFA_API int rfa_audio_rs_counts(int32_t L, int32_t D, int32_t r, size_t n, size_t *n_out, int32_t *r_next);
+/* Host only: ceil(n * L / D), the most outputs any call of n inputs writes; 0 for a ratio
+ * outside the limits or n above 2^36. */
+RFA_API size_t rfa_audio_rs_max_outputs(int32_t L, int32_t D, size_t n);
+/* Host only: what a call of one slot at offset 0 with n inputs runs: plan[0] the output tile of
+ * this ratio and tap count (at most RFA_AUDIO_RS_MAX_TILE; smaller where the tile's inputs would
+ * not fit the LDS), [1] the launch's dynamic LDS bytes, [2] the path, [3] outputs per thread
+ * (0 on NONE), [4] the slot's workgroups that do work.  RFA_ERR_INVALID for what
+ * rfa_audio_rs_create refuses, n above 2^36 or NULL. */
+RFA_API int rfa_audio_rs_plan(int32_t L, int32_t D, int32_t num_taps, size_t n, int32_t *plan);
+
+/* 1 <= n_channels <= RFA_AUDIO_RS_MAX_CHANNELS and the limits above; a non-finite tap, NULL
+ * taps with num_taps > 0 or a NULL out is RFA_ERR_INVALID.  Arguments are checked before the
+ * device is looked for.  Every slot starts with a zero history at offset 0. */
+RFA_API int rfa_audio_rs_create(int device, int32_t n_channels, int32_t L, int32_t D, const float *taps,
+                                int32_t num_taps, rfa_audio_rs **out);
+RFA_API int rfa_audio_rs_destroy(rfa_audio_rs *s);
+RFA_API const char *rfa_audio_rs_last_error(const rfa_audio_rs *s);
+RFA_API int rfa_audio_rs_get_channels(const rfa_audio_rs *s, int32_t *n_channels);
+RFA_API int rfa_audio_rs_get_ratio(const rfa_audio_rs *s, int32_t *L, int32_t *D);
+/* *num_taps is T; the taps are copied where capacity holds them (taps may be NULL with
+ * capacity 0 to ask for the count). */
+RFA_API int rfa_audio_rs_get_taps(const rfa_audio_rs *s, float *taps, size_t capacity, int32_t *num_taps);
+/* Slot k's history to zeros, ordered on the stream, and its offset to 0 (k = -1: every slot). */
+RFA_API int rfa_audio_rs_reset(rfa_audio_rs *s, int32_t k);
+/* Slot k's offset r as of the calls made so far. */
+RFA_API int rfa_audio_rs_get_offset(const rfa_audio_rs *s, int32_t k, int32_t *r);
+/* Device rows: in, in_stride floats apart, host counts n_audio[n_channels]; out_f32 rows
+ * f32_stride floats apart and out_s16 rows s16_stride int16 apart.  Either output may be NULL,
+ * not both.  n_out[n_channels] (host, may be NULL) is filled before the launch, from the rule
+ * above.  Asynchronous on the handle's stream: the call's records (counts, offsets, history
+ * buffers) go through a ring of pinned entries guarded by events, then one launch.  A
+ * steady-state call allocates nothing and waits for nothing.  Any 2-byte-aligned out_s16 and
+ * any s16_stride work: the kernel stores int16 one at a time.
+ * RFA_ERR_INVALID, nothing consumed: an input count above in_stride or an output count above an
+ * output's stride where n_channels > 1, a NULL input row or both outputs NULL with work to do,
+ * a NULL count array, an output range that overlaps the input or the other output, a float
+ * pointer off a 4-byte or an int16 pointer off a 2-byte boundary.
+ * RFA_ERR_UNSUPPORTED, nothing consumed: the taps' LDS image is above 64 KiB (rfa_audio_rs_plan
+ * reports it) and the device did not grant the launch that much. */
+RFA_API int rfa_audio_rs_process(rfa_audio_rs *s, const float *in, size_t in_stride, const size_t *n_audio,
+                                 float *out_f32, size_t f32_stride, int16_t *out_s16, size_t s16_stride,
+                                 size_t *n_out);
+/* rfa_audio_rs_process with host rows: synchronous. */
+RFA_API int rfa_audio_rs_process_host(rfa_audio_rs *s, const float *in, size_t in_stride, const size_t *n_audio,
+                                      float *out_f32, size_t f32_stride, int16_t *out_s16, size_t s16_stride,
+                                      size_t *n_out);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_audio_rs_set_stream(rfa_audio_rs *s, void *stream);
+RFA_API int rfa_audio_rs_get_stream(const rfa_audio_rs *s, void **stream);
+RFA_API int rfa_audio_rs_synchronize(rfa_audio_rs *s);
 
 #ifdef __cplusplus
 }

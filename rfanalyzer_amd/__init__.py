@@ -16,7 +16,9 @@ reference's interfaces for this path:
     demod.Demodulator          analyzer/Demodulator.kt + AudioSink.java: AM/FM/SSB/CW to 48 kHz audio
     demod.Receiver             FrontEnd chained into Demodulator, raw IQ bytes to audio
     demod.AudioFilterBank      (extension) a real FIR per bank slot on the audio rows; demod.voice_taps
-    scheduler.Scheduler        analyzer/Scheduler.kt packet fan-out
+    demod.AudioResamplerBank   (extension) every bank slot's audio by L / D to 8 / 16 kHz s16 PCM; demod.resampler_taps,
+                               pcm= on the bank chains, recording.AudioLogWriter
+    scheduler.Scheduler       analyzer/Scheduler.kt packet fan-out
 
 There is no CPU fallback: without librfa.so or a HIP device, calls raise.
 """

@@ -33,6 +33,15 @@ RFA_AUDIO_FIR_TILE = 2048
 RFA_AUDIO_FIR_NARROW_MAX = 512
 RFA_AUDIO_FIR_PATHS = ("none", "copy", "narrow", "wide")    # RFA_AUDIO_FIR_PATH_* in order
 RFA_AUDIO_FIR_PLAN_FIELDS = 5
+RFA_AUDIO_RS_MAX_CHANNELS = 1024
+RFA_AUDIO_RS_MAX_L = 160
+RFA_AUDIO_RS_MAX_D = 1024
+RFA_AUDIO_RS_MAX_TAPS = 16384
+RFA_AUDIO_RS_MAX_PHASE_TAPS = 4096
+RFA_AUDIO_RS_HISTORY = 4095
+RFA_AUDIO_RS_MAX_TILE = 1024
+RFA_AUDIO_RS_PATHS = ("none", "convert", "decimate", "polyphase")   # RFA_AUDIO_RS_PATH_* in order
+RFA_AUDIO_RS_PLAN_FIELDS = 5
 
 WINDOWS = {"blackman": 0, "hann": 1, "none": 2}
 FORMATS = {"s8": 0, "u8": 1, "s16": 2, "f32": 3, "f32p": 4}
@@ -359,6 +368,28 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_audio_fir_set_stream": (ctypes.c_int, [_h, _vp]),
         "rfa_audio_fir_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
         "rfa_audio_fir_synchronize": (ctypes.c_int, [_h]),
+        # audio resampler bank: every slot's audio row by L / D to s16 / f32 (rfanalyzer_amd/csrc/audio_rs.hip)
+        "rfa_audio_rs_counts": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t,
+                                               ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_rs_max_outputs": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t]),
+        "rfa_audio_rs_plan": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_size_t,
+                                             ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_rs_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _fp,
+                                               ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_audio_rs_destroy": (ctypes.c_int, [_h]),
+        "rfa_audio_rs_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_audio_rs_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_rs_get_ratio": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_rs_get_taps": (ctypes.c_int, [_h, _fp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_rs_reset": (ctypes.c_int, [_h, ctypes.c_int32]),
+        "rfa_audio_rs_get_offset": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_rs_process": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t, _vp,
+                                                ctypes.c_size_t, _vp]),
+        "rfa_audio_rs_process_host": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t, _vp,
+                                                     ctypes.c_size_t, _vp]),
+        "rfa_audio_rs_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_audio_rs_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_audio_rs_synchronize": (ctypes.c_int, [_h]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -42,6 +42,7 @@
 #include <new>
 #include <vector>
 
+#include "audio_hist.h"
 #include "stage_common.h"
 
 #pragma clang fp contract(off)
@@ -49,7 +50,7 @@
 namespace {
 
 constexpr int kMaxTaps = RFA_AUDIO_FIR_MAX_TAPS;
-constexpr int kHist = kMaxTaps - 1;
+constexpr int kHist = kAudioHist;               // hist_source(), audio_hist.h
 constexpr int kTile = RFA_AUDIO_FIR_TILE;
 constexpr int kNarrowMax = RFA_AUDIO_FIR_NARROW_MAX;
 constexpr int kThreads = 256;
@@ -58,6 +59,7 @@ constexpr int kSlack = 16;             // floats behind the staged samples that 
 constexpr int kRecRing = 8;
 constexpr size_t kMaxCount = (size_t)1 << 36;
 
+static_assert(kHist == kMaxTaps - 1, "the history holds what the longest filter reaches back");
 static_assert(kThreads * kWideR == kTile && kThreads * kNarrowR == kNarrowMax, "a thread's outputs fill the tile");
 
 struct FirSlot {
@@ -65,17 +67,6 @@ struct FirSlot {
     int taps;                          // T
     int cur;                           // the history buffer this call reads (it writes the other one)
 };
-
-// Sample j of the history after a call of n inputs, as a position in (history ++ inputs).
-__host__ __device__ inline bool hist_source(unsigned long long n, int j, unsigned long long &index) {
-    const unsigned long long at = n + (unsigned long long)j;
-    if (at < (unsigned long long)kHist) {
-        index = at;
-        return false;
-    }
-    index = at - (unsigned long long)kHist;
-    return true;
-}
 
 inline int round4(int v) { return (v + 3) & ~3; }
 

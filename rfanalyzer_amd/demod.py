@@ -49,6 +49,12 @@ retune their slots with the two.  The reference has no counterpart.
 (``rfa_audio_fir_*``): taps, history and count per slot, one launch per call; ``voice_taps`` is the
 300 Hz high-pass that takes a CTCSS tone out of the voice, and a bank chain built with
 ``audio_filter=`` hands out the filtered rows.  The reference has no counterpart.
+
+``AudioResamplerBank`` is the last stage of a K-channel voice logger (``rfa_audio_rs_*``): every
+slot's audio row resampled by one rational ratio L / D through one prototype FIR and written as int16
+PCM, float32 or both, one launch per call; ``resampler_taps`` designs the prototype, a bank chain
+built with ``pcm=8000`` leaves the PCM in ``pcm_tensor`` and hands it out through ``pcm()``, and
+``recording.AudioLogWriter`` writes one WAV per slot.  The reference has no counterpart.
 """
 from __future__ import annotations
 
@@ -1406,6 +1412,231 @@ class AudioFilterBank(_Handle):
         return [out[k, :c].copy() for k, c in enumerate(counts)]
 
 
+# ---------------------------------------------------------------- audio resampler bank
+
+AUDIO_RS_MAX_L = _lib.RFA_AUDIO_RS_MAX_L
+AUDIO_RS_MAX_D = _lib.RFA_AUDIO_RS_MAX_D
+AUDIO_RS_MAX_TAPS = _lib.RFA_AUDIO_RS_MAX_TAPS
+AUDIO_RS_MAX_PHASE_TAPS = _lib.RFA_AUDIO_RS_MAX_PHASE_TAPS
+AUDIO_RS_PLAN_FIELDS = ("tile", "lds_bytes", "path", "outputs_per_thread", "workgroups")    # rfa_audio_rs_plan order
+
+
+def _check_resampler_shape(L: int, D: int, num_taps: int) -> None:
+    """The limits of ``rfa_audio_rs_create`` as ``ValueError``s that name them.  Host only."""
+    if not 1 <= L <= AUDIO_RS_MAX_L:
+        raise ValueError(f"L = {L} outside 1 ... {AUDIO_RS_MAX_L}")
+    if not L <= D <= AUDIO_RS_MAX_D:
+        raise ValueError(f"D = {D} outside L = {L} ... {AUDIO_RS_MAX_D} (no up-sampling)")
+    if math.gcd(L, D) != 1:
+        raise ValueError(f"L / D = {L} / {D} is not reduced")
+    if not 0 <= num_taps <= AUDIO_RS_MAX_TAPS:
+        raise ValueError(f"{num_taps} taps, above {AUDIO_RS_MAX_TAPS}")
+    if num_taps == 0 and (L, D) != (1, 1):
+        raise ValueError("only L = D = 1 may have no taps")
+    if -(-num_taps // L) > AUDIO_RS_MAX_PHASE_TAPS:
+        raise ValueError(f"{-(-num_taps // L)} taps per phase, above {AUDIO_RS_MAX_PHASE_TAPS}")
+
+
+def resampler_taps(in_rate: int = AUDIO_RATE, out_rate: int = 8000, transition_hz: float | None = None,
+                   attenuation_db: float = 60.0):
+    """(L, D, float32 taps) of an ``AudioResamplerBank`` from ``in_rate`` to ``out_rate``: L / D is
+    out / in reduced and the prototype is the reference's own low-pass design at the rate L * in_rate
+    with gain L, ``create_low_pass_taps(L, L * in_rate, (pass + stop) / 2, stop - pass, attenuation_db)``
+    with the stopband edge ``stop`` at min(in, out) / 2 and the passband edge ``pass`` at 0.85 of it,
+    or at ``stop - transition_hz``.  219 taps at the defaults.  That design has its -6 dB point at the
+    cutoff, the middle of the transition band: the stopband edge itself is at -23 dB and the attenuation
+    asked for is reached about half a band above it (DESIGN.md 5.7n has the table).  ``ValueError``,
+    naming the limit, for a ratio or a tap count outside the handle's limits.  Host only."""
+    in_rate, out_rate = int(in_rate), int(out_rate)
+    if in_rate < 1 or out_rate < 1:
+        raise ValueError("rates must be positive")
+    g = math.gcd(in_rate, out_rate)
+    L, D = out_rate // g, in_rate // g
+    _check_resampler_shape(L, D, 1)
+    stop = min(in_rate, out_rate) / 2.0
+    width = 0.15 * stop if transition_hz is None else float(transition_hz)
+    if not (math.isfinite(width) and 0.0 < width < stop):
+        raise ValueError(f"transition_hz must lie between 0 and the stopband edge, {stop} Hz")
+    taps = create_low_pass_taps(float(L), float(L) * in_rate, stop - width / 2.0, width, float(attenuation_db))
+    if taps is None:
+        raise ValueError("the low-pass design rejected these arguments")
+    _check_resampler_shape(L, D, taps.size)
+    return L, D, taps.astype(np.float32)
+
+
+def audio_rs_counts(L: int, D: int, r: int, n: int) -> tuple[int, int]:
+    """(outputs, next offset) of a slot at offset ``r`` given ``n`` inputs (``rfa_audio_rs_counts``).  Host only."""
+    n_out, r_next = ctypes.c_size_t(0), ctypes.c_int32(0)
+    _lib.check(_lib.lib().rfa_audio_rs_counts(int(L), int(D), int(r), int(n), ctypes.byref(n_out), ctypes.byref(r_next)),
+               "rfa_audio_rs_counts")
+    return n_out.value, r_next.value
+
+
+def audio_rs_plan(L: int, D: int, num_taps: int, n: int) -> dict:
+    """What a call of one slot at offset 0 with ``n`` inputs runs (``rfa_audio_rs_plan``): ``tile`` (outputs per
+    workgroup), ``lds_bytes``, ``path`` ("none", "convert", "decimate", "polyphase"), ``outputs_per_thread``
+    and ``workgroups``.  Host only."""
+    out = (ctypes.c_int32 * _lib.RFA_AUDIO_RS_PLAN_FIELDS)()
+    _lib.check(_lib.lib().rfa_audio_rs_plan(int(L), int(D), int(num_taps), int(n), out), "rfa_audio_rs_plan")
+    plan = dict(zip(AUDIO_RS_PLAN_FIELDS, (int(v) for v in out)))
+    plan["path"] = _lib.RFA_AUDIO_RS_PATHS[plan["path"]]
+    return plan
+
+
+class AudioResamplerBank(_Handle):
+    """Each of ``n_channels`` audio rows resampled by L / D through one real prototype FIR and written
+    as int16 PCM, float32 or both (``rfa_audio_rs_*``, ``rfanalyzer_amd/csrc/audio_rs.hip``).  A slot
+    keeps its last 4095 inputs on the device and an offset r on the host; output m of a call has
+    u = r + m D, i = u // L, p = u % L and is ``((0 + h[p] x[i]) + h[p+L] x[i-1]) + ...`` with every
+    product and sum rounded to float32, so a stream cut into calls anywhere gives the bits and the
+    count of the stream given whole.  PCM is ``rint(y * 32768)`` clipped to int16, NaN as 0.  One
+    launch per call whatever the slot count; ``process_device`` is asynchronous on the handle's stream."""
+
+    _prefix = "rfa_audio_rs"
+
+    def __init__(self, n_channels: int, L: int, D: int, taps, device: int = 0):
+        self.n_channels = int(n_channels)
+        taps = np.ascontiguousarray(np.zeros(0) if taps is None else taps, np.float32)
+        if taps.ndim != 1:
+            raise ValueError("taps must be 1-D")
+        _check_resampler_shape(int(L), int(D), taps.size)
+        if not np.isfinite(taps).all():
+            raise ValueError("a tap is not finite")
+        self._create("rfa_audio_rs_create", device, self.n_channels, int(L), int(D),
+                     taps.ctypes.data_as(_lib._fp) if taps.size else None, taps.size)
+        self._ratio = (int(L), int(D))
+        self._n_out = (ctypes.c_size_t * self.n_channels)()
+
+    @classmethod
+    def for_rates(cls, n_channels: int, out_rate: int, in_rate: int = AUDIO_RATE, device: int = 0, **design):
+        """A bank from ``in_rate`` to ``out_rate`` with ``resampler_taps(in_rate, out_rate, **design)``."""
+        return cls(n_channels, *resampler_taps(in_rate, out_rate, **design), device=device)
+
+    @property
+    def ratio(self) -> tuple[int, int]:
+        """(L, D)."""
+        return self._ratio
+
+    @property
+    def taps(self) -> np.ndarray:
+        return self._query_floats("get_taps", 1, 1)[0][0]
+
+    def offset(self, k: int) -> int:
+        """Slot k's offset r as of the calls made so far."""
+        r = ctypes.c_int32(0)
+        self._call("get_offset", int(k), ctypes.byref(r))
+        return r.value
+
+    def reset(self, k: int | None = None) -> None:
+        """Slot k's history (None: every slot's) to zeros and its offset to 0."""
+        self._call("reset", -1 if k is None else int(k))
+
+    def max_outputs(self, n: int) -> int:
+        """ceil(n L / D): the most outputs a call of n inputs writes."""
+        return int(_lib.lib().rfa_audio_rs_max_outputs(*self._ratio, int(n)))
+
+    def plan(self, n: int, num_taps: int | None = None) -> dict:
+        return audio_rs_plan(*self._ratio, self.taps.size if num_taps is None else num_taps, n)
+
+    _count_array = AudioFilterBank._count_array
+
+    def process_device(self, in_ptr: int, in_stride: int, counts, f32_ptr: int | None, f32_stride: int,
+                       s16_ptr: int | None, s16_stride: int) -> list[int]:
+        """Device rows in (stride in floats), float32 rows and / or int16 rows out (strides in elements;
+        a pointer may be None, not both), one count per slot.  Enqueues on the handle's stream and returns
+        every slot's output count."""
+        self._call("process", in_ptr, in_stride, self._count_array(counts), f32_ptr or None, f32_stride,
+                   s16_ptr or None, s16_stride, self._n_out)
+        return list(self._n_out)
+
+    def process_tensor(self, audio, counts, out_s16=None, out_f32=None) -> list[int]:
+        """torch.cuda tensors [K, width]: float32 in, int16 and / or float32 out (rows may be slices of
+        wider tensors) and one count per slot; on torch's current stream.  Returns the output counts."""
+        self._follow_torch_stream(audio)
+        K = self.n_channels
+        if out_s16 is None and out_f32 is None:
+            raise ValueError("out_s16, out_f32 or both")
+        for t, dt in ((audio, "torch.float32"), (out_s16, "torch.int16"), (out_f32, "torch.float32")):
+            if t is None:
+                continue
+            if t.dim() != 2 or t.shape[0] != K or str(t.dtype) != dt:
+                raise ValueError(f"audio and out_f32 must be float32 and out_s16 int16, of shape [{K}, n]")
+            if t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("rows must be contiguous")
+        counts = self._count_array(counts)
+        if max(counts) > audio.shape[1]:
+            raise ValueError("a count above the rows' length")
+        need = self.max_outputs(max(counts))
+        if any(t is not None and t.shape[1] < need for t in (out_s16, out_f32)):
+            raise ValueError(f"output rows shorter than {need}")
+        stride = lambda t: 0 if t is None else t.stride(0) if K > 1 else t.shape[1]
+        return self.process_device(audio.data_ptr(), stride(audio), counts,
+                                   None if out_f32 is None else out_f32.data_ptr(), stride(out_f32),
+                                   None if out_s16 is None else out_s16.data_ptr(), stride(out_s16))
+
+    def process_both(self, rows, counts=None) -> tuple[list[np.ndarray], list[np.ndarray]]:
+        """Host float32 [K, width] rows and one count per slot (default: the width) -> (K int16 arrays,
+        K float32 arrays) of one call that writes both outputs."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[0] != self.n_channels:
+            raise ValueError(f"rows must have shape [{self.n_channels}, n]")
+        counts = self._count_array([rows.shape[1]] * self.n_channels if counts is None else counts)
+        if max(counts) > rows.shape[1]:
+            raise ValueError("a count above the rows' length")
+        width = max(self.max_outputs(max(counts)), 1)
+        pcm = np.zeros((self.n_channels, width), np.int16)
+        f32 = np.zeros((self.n_channels, width), np.float32)
+        self._call("process_host", rows.ctypes.data, rows.shape[1], counts, f32.ctypes.data, width, pcm.ctypes.data,
+                   width, self._n_out)
+        return ([pcm[k, :c].copy() for k, c in enumerate(self._n_out)],
+                [f32[k, :c].copy() for k, c in enumerate(self._n_out)])
+
+    def process(self, rows, counts=None, pcm: bool = True) -> list[np.ndarray]:
+        """Host float32 [K, width] rows and one count per slot (default: the width) -> K int16 arrays
+        (``pcm=False``: K float32 arrays)."""
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[0] != self.n_channels:
+            raise ValueError(f"rows must have shape [{self.n_channels}, n]")
+        counts = self._count_array([rows.shape[1]] * self.n_channels if counts is None else counts)
+        if max(counts) > rows.shape[1]:
+            raise ValueError("a count above the rows' length")
+        width = max(self.max_outputs(max(counts)), 1)
+        out = np.zeros((self.n_channels, width), np.int16 if pcm else np.float32)
+        ptrs = (None, 0, out.ctypes.data, width) if pcm else (out.ctypes.data, width, None, 0)
+        self._call("process_host", rows.ctypes.data, rows.shape[1], counts, *ptrs, self._n_out)
+        return [out[k, :c].copy() for k, c in enumerate(self._n_out)]
+
+
+def _pcm_entry(pcm):
+    """The ``pcm=`` keyword of a bank chain -> None or (L, D, taps).  Host only: a wrong entry raises
+    before any device work."""
+    if pcm is None:
+        return None
+    if isinstance(pcm, bool):
+        raise ValueError("pcm must be None, an output rate in Hz or a dict of AudioResamplerBank.for_rates keywords")
+    if isinstance(pcm, (int, np.integer)):
+        return resampler_taps(AUDIO_RATE, int(pcm))
+    if not isinstance(pcm, dict):
+        raise ValueError("pcm must be None, an output rate in Hz or a dict of AudioResamplerBank.for_rates keywords")
+    design = dict(pcm)
+    explicit = [key in design for key in ("L", "D", "taps")]
+    if any(explicit):
+        if not all(explicit) or len(design) != 3:
+            raise ValueError("an explicit resampler is exactly L, D and taps")
+        taps = np.ascontiguousarray(np.zeros(0) if design["taps"] is None else design["taps"], np.float32)
+        if taps.ndim != 1 or not np.isfinite(taps).all():
+            raise ValueError("taps must be 1-D and finite")
+        _check_resampler_shape(int(design["L"]), int(design["D"]), taps.size)
+        return int(design["L"]), int(design["D"]), taps
+    unknown = set(design) - {"out_rate", "in_rate", "transition_hz", "attenuation_db"}
+    if unknown or "out_rate" not in design:
+        raise ValueError(f"pcm takes out_rate, in_rate, transition_hz and attenuation_db; got {sorted(design)}")
+    if int(design.get("in_rate", AUDIO_RATE)) != AUDIO_RATE:
+        raise ValueError(f"a chain's audio rows run at {AUDIO_RATE} Hz")
+    design.pop("in_rate", None)
+    return resampler_taps(AUDIO_RATE, int(design.pop("out_rate")), **design)
+
+
 class _Chain:
     """What the receiver chains share: the context manager, the audio tensor and the staging of
     one host packet.  A chain has ``front``, ``_buffers``, ``process_device`` and ``close``."""
@@ -1577,9 +1808,22 @@ class _BankChain(_Chain):
     on every call with the demodulator bank's own counts (``audio_counts``) -- not the tone-gated
     ones, so a slot's filtered stream is continuous across closed gates -- into a second row tensor,
     which ``audio_tensor`` and ``process`` then return.  The tone meter keeps reading the
-    demodulators' rows: it needs the tone.  The reported counts stay as without the filter."""
+    demodulators' rows: it needs the tone.  The reported counts stay as without the filter.
+
+    ``pcm``: None (no resampler handle, no PCM buffer, nothing more enqueued), an output rate in Hz, or a
+    dict of ``AudioResamplerBank.for_rates`` keywords (``out_rate``, ``transition_hz``,
+    ``attenuation_db``) or of exactly ``L``, ``D`` and ``taps``.  The chain then owns an
+    ``AudioResamplerBank`` (``audio_rs``) that runs last on every call, on the rows ``audio_tensor``
+    returns and with the demodulator bank's own counts -- the ungated ones, so a slot's PCM stream
+    stays continuous across closed tone gates, as the filter's does -- into an int16 ``[K, cap]``
+    tensor, ``pcm_tensor``.  ``pcm_counts`` are the last call's ungated output counts; ``pcm()``
+    waits for the stream and returns K int16 arrays, empty for a slot whose reported audio count in
+    this call is 0 (squelch-held or tone-closed).  ``process`` and its counts stay as they are."""
 
     squelch = None
+    _pcm = None                # the resampler's int16 rows; the handle is self.audio_rs, present only with pcm=
+    _pcm_counts = None
+    _reported = None           # the last call's reported counts, kept only with pcm=
     _filtered = None           # the filter's rows; the handle is self.audio_fir, present only with audio_filter=
     _audio_counts = None
     _tone = None               # the ToneRule; the meter handle is self.tone_meter, present only with tone=
@@ -1587,12 +1831,13 @@ class _BankChain(_Chain):
     _nominal = None            # (frequency, [channel frequencies]) of the user's set_frequencies
 
     def __init__(self, input_format: str, sample_rate: int, modes, rate: int, device: int, *front_args,
-                 squelch=None, afc=None, tone=None, audio_filter=None):
+                 squelch=None, afc=None, tone=None, audio_filter=None, pcm=None):
         import torch
 
         rule, self._afc_default_limit = _afc_rule(afc, modes, rate)
         probes = _tone_entries(tone, len(modes))
         filters = _audio_filter_entries(audio_filter, len(modes))
+        resampler = _pcm_entry(pcm)
         self._torch = torch
         self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
         self._tdev = torch.device("cuda", device)
@@ -1625,6 +1870,8 @@ class _BankChain(_Chain):
                 for k, taps in enumerate(filters):
                     if taps is not None:
                         self.audio_fir.set_taps(k, taps)
+            if resampler is not None:
+                self.audio_rs = AudioResamplerBank(self._n_channels, *resampler, device=device)
             self.set_stream(None)
         except Exception:
             self.close()
@@ -1721,6 +1968,28 @@ class _BankChain(_Chain):
         the first call): what the rows of ``audio_tensor`` hold."""
         return None if self._audio_counts is None else list(self._audio_counts)
 
+    @property
+    def pcm_tensor(self):
+        """The int16 ``[K, cap]`` rows the resampler wrote in the last call; None without ``pcm=``."""
+        return self._pcm
+
+    @property
+    def pcm_counts(self):
+        """The resampler's output counts of the last call, before any gate (list[int]; None before the
+        first call or without ``pcm=``): what the rows of ``pcm_tensor`` hold."""
+        return None if self._pcm_counts is None else list(self._pcm_counts)
+
+    def pcm(self) -> list[np.ndarray]:
+        """The last call's PCM: waits for the stream; K int16 arrays cut to ``pcm_counts``, empty for a
+        slot whose reported audio count in that call is 0."""
+        if not hasattr(self, "audio_rs"):
+            raise ValueError("this chain was built without a resampler (pcm=None)")
+        if self._pcm_counts is None:
+            return [np.zeros(0, np.int16) for _ in range(self._n_channels)]
+        self.demods.synchronize()
+        rows = self._pcm.cpu().numpy()
+        return [rows[k, :c if g else 0].copy() for k, (c, g) in enumerate(zip(self._pcm_counts, self._reported))]
+
     def _audio_fir(self) -> AudioFilterBank:
         if not hasattr(self, "audio_fir"):
             raise ValueError("this chain was built without an audio filter (audio_filter=None)")
@@ -1783,6 +2052,8 @@ class _BankChain(_Chain):
             self.tone_meter.set_stream(self.demods.stream)
         if hasattr(self, "audio_fir"):
             self.audio_fir.set_stream(self.demods.stream)
+        if hasattr(self, "audio_rs"):
+            self.audio_rs.set_stream(self.demods.stream)
 
     def synchronize(self) -> None:
         self.demods.synchronize()
@@ -1799,6 +2070,9 @@ class _BankChain(_Chain):
             self._audio = torch.empty(shape, dtype=torch.float32, device=self._tdev)
             if hasattr(self, "audio_fir"):
                 self._filtered = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+            if hasattr(self, "audio_rs"):
+                self._pcm = torch.empty((self.n_channels, max(self.audio_rs.max_outputs(cap), 1)), dtype=torch.int16,
+                                        device=self._tdev)
         return self._re.shape[1]
 
     def process_device(self, raw_ptr: int, n_samples: int) -> list[int]:
@@ -1828,7 +2102,14 @@ class _BankChain(_Chain):
         if self._filtered is not None:
             self.audio_fir._call("process", self._audio.data_ptr(), cap, self.demods._counts,
                                  self._filtered.data_ptr(), cap)
-        return counts if self._tone is None else self._step_tone(counts, cap)
+        if self._tone is not None:
+            counts = self._step_tone(counts, cap)
+        if self._pcm is not None:
+            rs = self.audio_rs
+            rs._call("process", self.audio_tensor.data_ptr(), cap, self.demods._counts, None, 0, self._pcm.data_ptr(),
+                     self._pcm.shape[1], rs._n_out)
+            self._pcm_counts, self._reported = list(rs._n_out), counts
+        return counts
 
     def process(self, raw_bytes) -> list[np.ndarray]:
         """One raw input packet (host bytes) -> K float32 audio arrays."""
@@ -1855,6 +2136,10 @@ class _BankChain(_Chain):
             self.audio_fir.close()
             del self.audio_fir
             self._filtered = None
+        if hasattr(self, "audio_rs"):
+            self.audio_rs.close()
+            del self.audio_rs
+            self._pcm = None
         if self.demods is not None:
             self.demods.close()
             self.demods = None
@@ -1869,10 +2154,10 @@ class ReceiverBank(_BankChain):
     Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
 
     def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0, *, squelch=None, afc=None,
-                 tone=None, audio_filter=None):
+                 tone=None, audio_filter=None, pcm=None):
         self._cap_for = (None, 0)
         super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch, afc=afc, tone=tone,
-                         audio_filter=audio_filter)
+                         audio_filter=audio_filter, pcm=pcm)
 
     def _make_front(self):
         return FrontEndBank(self.input_format, self.sample_rate, self.quadrature_rate, self.n_channels, self.device,
@@ -2206,7 +2491,7 @@ class RasterReceiverBank(_BankChain):
     quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``)."""
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0,
-                 resample: bool = False, *, squelch=None, afc=None, tone=None, audio_filter=None):
+                 resample: bool = False, *, squelch=None, afc=None, tone=None, audio_filter=None, pcm=None):
         if afc is not None and afc is not False:
             raise ValueError("a RasterReceiverBank cannot tune: its prototype passes one raster channel per slot and "
                              "leaves no room to move; use a TunedReceiverBank for AFC")
@@ -2216,7 +2501,7 @@ class RasterReceiverBank(_BankChain):
             raise ValueError(f"{len(modes)} channels expected, got {len(channels)}")
         self._resample = bool(resample)
         super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, channels, squelch=squelch,
-                         tone=tone, audio_filter=audio_filter)
+                         tone=tone, audio_filter=audio_filter, pcm=pcm)
 
     def _make_front(self, spacing_hz: int, channels):
         make = Channelizer.for_raster_resampled if self._resample else Channelizer.for_raster
@@ -2253,14 +2538,14 @@ class TunedReceiverBank(_BankChain):
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, device: int = 0,
                  resample: bool = False, *, squelch=None, passband_hz: float | None = None, afc=None, tone=None,
-                 audio_filter=None):
+                 audio_filter=None, pcm=None):
         modes, rate = _common_rate(modes)
         if passband_hz is None:
             passband_hz = int(spacing_hz) / 2 + max(mode_info(m)[2] for m in modes)
         self.passband_hz = float(passband_hz)
         self._resample = bool(resample)
         super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch, afc=afc,
-                         tone=tone, audio_filter=audio_filter)
+                         tone=tone, audio_filter=audio_filter, pcm=pcm)
 
     def _make_front(self, spacing_hz: int):
         front = Channelizer.for_channels(self.input_format, self.sample_rate, spacing_hz, self.quadrature_rate,

@@ -156,3 +156,66 @@ class RecordingWriter:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class AudioLogWriter:
+    """One mono s16 WAV file per bank slot (an extension: the reference records IQ, not audio), written
+    with the stdlib ``wave`` module: ``{directory}/{name}.wav`` for every name, at ``rate`` Hz.
+    ``write(arrays)`` takes one int16 array per slot -- what a bank chain's ``pcm()`` returns -- and
+    appends the non-empty ones; ``close()`` finalises the headers and returns
+    ``{name: (path, samples written)}``.  A context manager."""
+
+    def __init__(self, directory: str, names, rate: int):
+        import wave
+
+        names = [str(n) for n in names]
+        if not names or len(set(names)) != len(names):
+            raise ValueError("one distinct name per slot")
+        if any(not n or os.sep in n or (os.altsep and os.altsep in n) or n in (".", "..") for n in names):
+            raise ValueError("a name must be a plain file name")
+        if int(rate) != rate or not 1 <= int(rate) <= 0xFFFFFFFF:
+            raise ValueError("rate must be a whole number of Hz")
+        self.names, self.rate = names, int(rate)
+        self.paths = [os.path.join(directory, n + ".wav") for n in names]
+        self.samples = [0] * len(names)
+        self._files = []
+        os.makedirs(directory, exist_ok=True)
+        try:
+            for path in self.paths:
+                w = wave.open(path, "wb")
+                self._files.append(w)
+                w.setnchannels(1)
+                w.setsampwidth(2)
+                w.setframerate(self.rate)
+        except Exception:
+            self.close()
+            raise
+
+    def write(self, arrays) -> None:
+        """One int16 array per slot; an empty one (a closed slot) appends nothing."""
+        import numpy as np
+
+        if not self._files:
+            raise ValueError("the writer is closed")
+        arrays = list(arrays)
+        if len(arrays) != len(self.names):
+            raise ValueError(f"{len(self.names)} arrays expected, got {len(arrays)}")
+        for a in arrays:
+            if not isinstance(a, np.ndarray) or a.dtype != np.int16 or a.ndim != 1:
+                raise ValueError("1-D int16 arrays expected")
+        for k, a in enumerate(arrays):
+            if a.size:
+                self._files[k].writeframes(a.astype("<i2", copy=False).tobytes())
+                self.samples[k] += a.size
+
+    def close(self) -> dict:
+        for w in self._files:
+            w.close()
+        self._files = []
+        return {n: (p, c) for n, p, c in zip(self.names, self.paths, self.samples)}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
