@@ -37,6 +37,7 @@
  *     rfa_pfb_create_rational: at any source sample rate)
  *   (extension) frequency error of every bank slot         rfa_freq_*() (frequency meter bank, below)
  *   (extension) CTCSS tone sums of every bank slot's audio rfa_tone_*() (tone meter bank, below)
+ *   (extension) DCS sub-cell sums of every bank slot's audio rfa_code_*() (code meter bank, below)
  *   (extension) a real FIR on every bank slot's audio      rfa_audio_fir_*() (audio FIR bank, below)
  *   (extension) every bank slot's audio to 8 / 16 kHz PCM  rfa_audio_rs_*() (audio resampler bank, below)
  *   (north-star extension) exponential average             rfa_get_ema()
@@ -1160,6 +1161,92 @@ RFA_API int rfa_tone_process_host(rfa_tone *t, const float *audio, size_t audio_
 RFA_API int rfa_tone_set_stream(rfa_tone *t, void *stream);
 RFA_API int rfa_tone_get_stream(const rfa_tone *t, void **stream);
 RFA_API int rfa_tone_synchronize(rfa_tone *t);
+
+/* ---------------------------------------------------------------------------
+ * Code meter bank (extension): what a DCS code squelch reads of every slot's audio
+ *
+ * DCS (digital-coded squelch, CDCSS) is a 23-bit word sent continuously under the voice
+ * at 134.4 bit/s = 672/5 Hz, NRZ, bit 0 first: bits 0 ... 8 the 9-bit code (three octal
+ * digits), bits 9 ... 11 = 0, 0, 1, bits 12 ... 22 the parity of the systematic Golay
+ * (23,12) code with generator 0xC75 (rfa_code_word).  The device sums, per slot, the
+ * quantised audio over sub-cells, RFA_CODE_SUBCELLS to the bit; the host carries an
+ * incomplete last sub-cell to the next call (rfa_code_merge) and correlates cells with
+ * the wanted word (demod.CodeRule).  The reference has nothing like this.
+ *
+ * Audio at sample_rate Hz (an integer, RFA_CODE_MIN_RATE ... RFA_CODE_MAX_RATE).  Every
+ * slot has a sample counter g, 0 at first and after rfa_code_break, limited to
+ * g <= 2^48 (672 * RFA_CODE_SUBCELLS * g stays below 2^61; a call that would pass the
+ * limit is RFA_ERR_INVALID).  Sample g belongs to sub-cell
+ *     s(g) = floor(672 * RFA_CODE_SUBCELLS * g / (5 * sample_rate))    in 64-bit integers
+ * and contributes
+ *     q(a) = llrint((double)a * 2^24)                                  ties to even
+ * or 0 where a is not finite or |a| >= 2^15; such a sample is counted in the slot's bad
+ * count of the call instead.  A call with counter g0 and n_k samples produces
+ *     S[j] = sum of q(a[i]) over s(g0 + i) = j,  j = s(g0) ... s(g0 + n_k - 1)   (int64)
+ * The sums are exact integers, so they do not depend on the order of the additions, the
+ * tiling, n_channels, the stride or the address: bit-identical from run to run, and a row
+ * cut into calls anywhere gives the completed sub-cells of the row given whole.  One
+ * launch per call whatever n_channels; a slot with n_k = 0 writes nothing; a call whose
+ * counts are all 0 launches nothing.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_code rfa_code;
+
+#define RFA_CODE_MAX_CHANNELS 1024             /* n_channels above this: RFA_ERR_INVALID */
+#define RFA_CODE_MIN_RATE 8000
+#define RFA_CODE_MAX_RATE 384000
+#define RFA_CODE_SUBCELLS 8                    /* P: sub-cells per bit */
+#define RFA_CODE_WORD_BITS 23
+
+/* Host only, no device: s(g) for 0 <= g <= 2^48.  RFA_ERR_INVALID for a rate outside the range,
+ * g outside the limit or a NULL pointer. */
+RFA_API int rfa_code_subcell(int32_t sample_rate, int64_t g, int64_t *j);
+/* Host only: the 23-bit word of a 9-bit code (0 ... 0x1ff; 023 octal -> 0x763813), bit i of
+ * the result being bit i on the air. */
+RFA_API int rfa_code_word(int32_t code, uint32_t *word);
+/* Host only: the carry arithmetic of one slot and call.  sums[m] are the call's touched
+ * sub-cells j0 ... j0 + m - 1, g_end the slot's counter behind the call.  A valid carry
+ * (whose carry_j must be j0) is added to sums[0]; where the next sample still falls into the
+ * last sub-cell (s(g_end) = j0 + m - 1) that one becomes the carry and is held back.  On
+ * return *first = j0 and *count completed sub-cells stand in sums[0 ... *count - 1].  m = 0
+ * leaves the carry as it is. */
+RFA_API int rfa_code_merge(int32_t sample_rate, int64_t g_end, int64_t j0, int64_t m, int64_t *sums,
+                           int32_t *carry_valid, int64_t *carry_j, int64_t *carry_sum, int64_t *first,
+                           int64_t *count);
+
+/* 1 <= n_channels <= RFA_CODE_MAX_CHANNELS and a rate in range; arguments are checked before
+ * the device is looked for. */
+RFA_API int rfa_code_create(int device, int32_t n_channels, int32_t sample_rate, rfa_code **out);
+RFA_API int rfa_code_destroy(rfa_code *t);
+RFA_API const char *rfa_code_last_error(const rfa_code *t);
+RFA_API int rfa_code_get_channels(const rfa_code *t, int32_t *n_channels, int32_t *sample_rate);
+/* Slot k's sample counter (k = -1: every slot's) back to 0 and its carry dropped; what an
+ * uncollected call holds of the slot is dropped too (its collect reports 0 sub-cells). */
+RFA_API int rfa_code_break(rfa_code *t, int32_t k);
+/* Every counter to 0, every carry dropped, the last results to 0, no call outstanding. */
+RFA_API int rfa_code_reset(rfa_code *t);
+/* Device rows audio_stride floats apart, host counts n_audio[n_channels] (what
+ * rfa_demod_bank_process returns).  Asynchronous: the call's records go through a ring of
+ * pinned entries guarded by events, then the launch, one copy of the sums into pinned memory
+ * and an event, all on the handle's stream; the buffers grow on demand.  The carry needs
+ * every call collected once: a call while the previous one is uncollected is RFA_ERR_STATE.
+ * A count above audio_stride where n_channels > 1, or a NULL row or count array with any
+ * count > 0, is RFA_ERR_INVALID; nothing is consumed on an error. */
+RFA_API int rfa_code_process(rfa_code *t, const float *audio, size_t audio_stride, const size_t *n_audio);
+/* Waits for the last rfa_code_process's event alone, merges the carries and hands out, per
+ * slot: the absolute index of the first completed sub-cell, their number, their sums (row k
+ * at sums + k * sums_stride), the call's bad count and its sample count; any may be NULL.
+ * A number above sums_stride is RFA_ERR_SIZE and the results stay collectable.  Without a
+ * call since the last collect it waits for nothing and repeats the values. */
+RFA_API int rfa_code_collect(rfa_code *t, int64_t *first, int64_t *count, int64_t *sums, size_t sums_stride,
+                             int64_t *bad, int64_t *n);
+/* rfa_code_process with host rows, then rfa_code_collect: synchronous. */
+RFA_API int rfa_code_process_host(rfa_code *t, const float *audio, size_t audio_stride, const size_t *n_audio,
+                                  int64_t *first, int64_t *count, int64_t *sums, size_t sums_stride, int64_t *bad,
+                                  int64_t *n);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_code_set_stream(rfa_code *t, void *stream);
+RFA_API int rfa_code_get_stream(const rfa_code *t, void **stream);
+RFA_API int rfa_code_synchronize(rfa_code *t);
 
 /* ---------------------------------------------------------------------------
  * Audio FIR bank (extension): a real FIR on every bank slot's audio row

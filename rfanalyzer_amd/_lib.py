@@ -350,6 +350,26 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_tone_set_stream": (ctypes.c_int, [_h, _vp]),
         "rfa_tone_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
         "rfa_tone_synchronize": (ctypes.c_int, [_h]),
+        # code meter bank: DCS sub-cell sums of every slot's audio row (rfanalyzer_amd/csrc/code.hip)
+        "rfa_code_subcell": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+        "rfa_code_word": (ctypes.c_int, [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32)]),
+        "rfa_code_merge": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp,
+                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.POINTER(ctypes.c_int64)]),
+        "rfa_code_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_code_destroy": (ctypes.c_int, [_h]),
+        "rfa_code_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_code_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_code_break": (ctypes.c_int, [_h, ctypes.c_int32]),
+        "rfa_code_reset": (ctypes.c_int, [_h]),
+        "rfa_code_process": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp]),
+        "rfa_code_collect": (ctypes.c_int, [_h, _vp, _vp, _vp, ctypes.c_size_t, _vp, _vp]),
+        "rfa_code_process_host": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp,
+                                                 _vp]),
+        "rfa_code_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_code_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_code_synchronize": (ctypes.c_int, [_h]),
         # audio FIR bank: a real FIR per slot on the audio rows (rfanalyzer_amd/csrc/audio_fir.hip)
         "rfa_audio_fir_plan": (ctypes.c_int, [ctypes.c_int32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)]),
         "rfa_audio_fir_history_source": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_int32,

@@ -45,6 +45,12 @@ the lag-1 autocorrelation of the quadrature rows, summed on the device); ``AfcRu
 per-slot control rule on the host, and ``ReceiverBank`` / ``TunedReceiverBank`` built with ``afc=``
 retune their slots with the two.  The reference has no counterpart.
 
+``CodeMeterBank`` sums every slot's quantised audio over the sub-cells of the 134.4 bit/s DCS bit
+(``rfa_code_*``: exact int64 sums, an incomplete sub-cell carried to the next call); ``CodeRule``
+correlates the cells with the wanted 23-bit word (``dcs_word``, ``dcs_parse``, ``DCS_CODES``;
+``dcs_identify`` searches the table), and a bank chain built with ``code=`` reports no audio for a
+slot whose code gate is closed.  The reference has no counterpart.
+
 ``AudioFilterBank`` is a real FIR on every slot's audio row behind the demodulator bank
 (``rfa_audio_fir_*``): taps, history and count per slot, one launch per call; ``voice_taps`` is the
 300 Hz high-pass that takes a CTCSS tone out of the voice, and a bank chain built with
@@ -1255,6 +1261,335 @@ class ToneRule:
         return self.open
 
 
+# ---------------------------------------------------------------- DCS code squelch
+
+# The 104 standard DCS codes (three octal digits each).
+DCS_CODES = tuple(int(c, 8) for c in (
+    "023 025 026 031 032 036 043 047 051 053 054 065 071 072 073 074 114 115 116 122 125 131 132 134 143 145 152 "
+    "155 156 162 165 172 174 205 212 223 225 226 243 244 245 246 251 252 255 261 263 265 266 271 274 306 311 315 "
+    "325 331 332 343 346 351 356 364 365 371 411 412 413 423 431 432 445 446 452 454 455 462 464 465 466 503 506 "
+    "516 523 526 532 546 565 606 612 624 627 631 632 654 662 664 703 712 723 731 732 734 743 754").split())
+CODE_SUBCELLS = 8                # RFA_CODE_SUBCELLS: P, sub-cells per bit
+CODE_WORD_BITS = 23
+_CODE_NUM = 672 * CODE_SUBCELLS  # s(g) = _CODE_NUM * g // (5 * rate)
+
+
+def dcs_word(code: int) -> int:
+    """The 23-bit word of a 9-bit code, bit i being bit i on the air: the code in bits 0 ... 8, 0, 0, 1 in
+    bits 9 ... 11 and in bits 12 ... 22 the parity of the systematic Golay (23,12) code with generator
+    ``0xC75`` -- the remainder of ``d x^11`` by it over GF(2).  ``dcs_word(0o023) == 0x763813``.  Host only."""
+    code = int(code)
+    if not 0 <= code <= 0x1FF:
+        raise ValueError("a DCS code has 9 bits (three octal digits)")
+    d = 0x800 | code
+    r = d << 11
+    for b in range(22, 10, -1):
+        if r >> b & 1:
+            r ^= 0xC75 << (b - 11)
+    return d | r << 12
+
+
+def dcs_parse(entry) -> tuple[int, bool]:
+    """``"023"``, ``"023N"``, ``"023I"`` (three octal digits, N normal, I inverted) or an int such as
+    ``0o023`` -> (code, inverted).  Any 9-bit code is taken, not only those of ``DCS_CODES``."""
+    if isinstance(entry, bool) or not isinstance(entry, (str, int, np.integer)):
+        raise TypeError("a DCS code is a string such as '023', '023N' or '023I', or an int such as 0o023")
+    if not isinstance(entry, str):
+        if not 0 <= int(entry) <= 0x1FF:
+            raise ValueError("a DCS code has 9 bits (three octal digits)")
+        return int(entry), False
+    text = entry.strip().upper()
+    inverted = text.endswith("I")
+    if text.endswith(("N", "I")):
+        text = text[:-1]
+    if len(text) != 3 or any(c not in "01234567" for c in text):
+        raise ValueError(f"DCS code {entry!r}: three octal digits and an optional N or I expected")
+    return int(text, 8), inverted
+
+
+@functools.lru_cache(maxsize=256)
+def _dcs_patterns(word: int, words: int) -> np.ndarray:
+    """The 23 rotations of a word as mean-removed +-1 cell patterns, tiled: float64 [23, 23 * words], each
+    row of norm 1.  Row r, cell i: bit (i + r) mod 23."""
+    bits = np.array([1.0 if word >> i & 1 else -1.0 for i in range(CODE_WORD_BITS)])
+    rows = np.stack([np.tile(np.roll(bits, -r), words) for r in range(CODE_WORD_BITS)])
+    rows -= rows.mean(axis=1, keepdims=True)
+    rows /= np.sqrt((rows * rows).sum(axis=1, keepdims=True))
+    rows.setflags(write=False)
+    return rows
+
+
+def _dcs_cells(subcells, words: int) -> np.ndarray:
+    """``P * (23 * words + 1)`` sub-cells -> the mean-removed, normalised cell values of the P timing
+    phases, float64 [P, 23 * words]; a phase without variance is a row of zeros."""
+    P, n = CODE_SUBCELLS, CODE_WORD_BITS * words
+    sub = np.asarray(subcells, np.float64)
+    x = np.stack([sub[p:p + P * n].reshape(n, P).sum(axis=1) for p in range(P)])
+    x -= x.mean(axis=1, keepdims=True)
+    norm = np.sqrt((x * x).sum(axis=1, keepdims=True))
+    return np.divide(x, norm, out=np.zeros_like(x), where=norm > 0)
+
+
+def dcs_score(subcells, word: int, words: int) -> float:
+    """The largest signed normalised correlation of the cells with ``word`` over the P timing phases
+    and the 23 rotations; 0 where the cells have no variance."""
+    return float((_dcs_cells(subcells, words) @ _dcs_patterns(int(word), int(words)).T).max())
+
+
+@functools.lru_cache(maxsize=4)
+def _dcs_table(words: int) -> np.ndarray:
+    out = np.concatenate([_dcs_patterns(dcs_word(c), words) for c in DCS_CODES])
+    out.setflags(write=False)
+    return out
+
+
+def dcs_identify(subcells, words: int) -> tuple[int, bool, float]:
+    """The search for an unknown code: the best (code, inverted, rho) over ``DCS_CODES`` and both
+    polarities on ``P * (23 * words + 1)`` sub-cells (more are ignored).  An inverted word is another
+    code's normal word (023I is 047N), and the complement of every code of ``DCS_CODES`` is in the table:
+    the normal reading is returned unless the inverted one scores higher by more than 1e-9."""
+    words = int(words)
+    need = CODE_SUBCELLS * (CODE_WORD_BITS * words + 1)
+    sub = np.asarray(subcells)
+    if sub.ndim != 1 or sub.size < need:
+        raise ValueError(f"{need} sub-cells expected for {words} words")
+    rho = (_dcs_cells(sub[:need], words) @ _dcs_table(words).T).reshape(CODE_SUBCELLS, len(DCS_CODES), CODE_WORD_BITS)
+    per_code = rho.max(axis=(0, 2)), (-rho).max(axis=(0, 2))
+    best = [int(np.argmax(p)) for p in per_code]
+    inverted = bool(per_code[1][best[1]] > per_code[0][best[0]] + 1e-9)
+    return DCS_CODES[best[inverted]], inverted, float(per_code[inverted][best[inverted]])
+
+
+def _code_entries(code, n_channels: int, tone=None):
+    """The ``code=`` keyword of a bank chain -> None or (code, inverted) or None per slot.  Host only: a
+    wrong keyword raises before any handle is made."""
+    if code is None:
+        return None
+    if isinstance(code, (bool, str, bytes, int, float)) or not hasattr(code, "__iter__"):
+        raise TypeError("code must be None or one entry per slot (a DCS code such as '023' or None)")
+    entries = list(code)
+    if len(entries) != n_channels:
+        raise ValueError(f"{n_channels} codes expected, got {len(entries)}")
+    parsed = [None if e is None else dcs_parse(e) for e in entries]
+    if tone is not None:
+        for k, (c, t) in enumerate(zip(parsed, tone)):
+            if c is not None and t is not None:
+                raise ValueError(f"slot {k} has both a tone and a code")
+    return parsed
+
+
+class CodeMeterBank(_Handle):
+    """Code meter for ``n_channels`` slots of audio at ``sample_rate`` (``rfa_code_*``,
+    ``rfanalyzer_amd/csrc/code.hip``): per call and slot the int64 sums of the quantised audio,
+    ``llrint(a * 2^24)``, over sub-cells, 8 to the 134.4 bit/s bit, indexed from the slot's last
+    ``break_``; a sample that is not finite or has ``|a| >= 2^15`` adds 0 and is counted as bad.  The
+    handle carries an incomplete last sub-cell to the next call, so the completed sub-cells of any
+    sequence of calls are the whole stream's, bit for bit.  ``process_device`` is asynchronous and every
+    call must be collected once; ``collect`` waits for that call's copy alone."""
+
+    _prefix = "rfa_code"
+
+    def __init__(self, n_channels: int, sample_rate: int = AUDIO_RATE, device: int = 0):
+        self.n_channels, self.sample_rate = int(n_channels), int(sample_rate)
+        self._create("rfa_code_create", device, self.n_channels, self.sample_rate)
+        K = self.n_channels
+        self._first, self._count = np.zeros(K, np.int64), np.zeros(K, np.int64)
+        self._bad, self._n = np.zeros(K, np.int64), np.zeros(K, np.int64)
+        self._sums = np.zeros((K, 64), np.int64)
+
+    def max_subcells(self, n: int) -> int:
+        """An upper bound of the sub-cells that ``n`` samples of a slot complete, a carry included."""
+        return int(n) * _CODE_NUM // (5 * self.sample_rate) + 2
+
+    def _room(self, n: int) -> None:
+        if self._sums.shape[1] < self.max_subcells(n):
+            self._sums = np.zeros((self.n_channels, self.max_subcells(n)), np.int64)
+
+    def break_(self, k: int | None = None) -> None:
+        """Slot k's sample counter (None: every slot's) back to 0, its carry dropped.  Host only."""
+        self._call("break", -1 if k is None else int(k))
+
+    def reset(self) -> None:
+        """Every counter to 0, every carry dropped, no call outstanding."""
+        self._call("reset")
+
+    _count_array = ToneMeterBank._count_array
+
+    def _out(self):
+        return (self._first.ctypes.data, self._count.ctypes.data, self._sums.ctypes.data, self._sums.shape[1],
+                self._bad.ctypes.data, self._n.ctypes.data)
+
+    def _result(self):
+        return (self._first.copy(), [self._sums[k, :c].copy() for k, c in enumerate(self._count)], self._bad.copy(),
+                self._n.copy())
+
+    def process_device(self, audio_ptr: int, audio_stride: int, counts) -> None:
+        """Device rows ``audio_stride`` floats apart, one count per slot.  Enqueues the sums and their copy
+        on the handle's stream and returns; ``RfaError`` (``RFA_ERR_STATE``) while a call is uncollected."""
+        counts = self._count_array(counts)
+        self._call("process", audio_ptr, audio_stride, counts)
+        self._room(max(counts))
+
+    def collect(self):
+        """(first int64[K], K int64 arrays of completed sub-cell sums, bad int64[K], n int64[K]) of the
+        last ``process_device``; waits for that call's copy and nothing else."""
+        self._call("collect", *self._out())
+        return self._result()
+
+    def process(self, audio, counts=None):
+        """Host float32 [K, width] rows and one count per slot (default: the width) -> as ``collect``."""
+        audio = np.ascontiguousarray(audio, np.float32)
+        if audio.ndim != 2 or audio.shape[0] != self.n_channels:
+            raise ValueError(f"audio must have shape [{self.n_channels}, n]")
+        counts = self._count_array([audio.shape[1]] * self.n_channels if counts is None else counts)
+        if max(counts) > audio.shape[1]:
+            raise ValueError("a count above the rows' length")
+        self._room(max(counts))
+        self._call("process_host", audio.ctypes.data, audio.shape[1], counts, *self._out())
+        return self._result()
+
+    def process_tensor(self, audio, counts):
+        """A torch.cuda float32 tensor [K, width] (rows may be slices of a wider tensor) and one count
+        per slot -> as ``collect``; on torch's current stream."""
+        self._follow_torch_stream(audio)
+        K = self.n_channels
+        if audio.dim() != 2 or audio.shape[0] != K or str(audio.dtype) != "torch.float32":
+            raise ValueError(f"audio must be float32 of shape [{K}, n]")
+        if audio.shape[1] > 1 and audio.stride(1) != 1:
+            raise ValueError("rows must be contiguous")
+        counts = self._count_array(counts)
+        if max(counts) > audio.shape[1]:
+            raise ValueError("a count above the rows' length")
+        self.process_device(audio.data_ptr(), audio.stride(0) if K > 1 else audio.shape[1], counts)
+        return self.collect()
+
+
+class CodeRule:
+    """DCS code squelch for ``n_channels`` slots: what to do with the sub-cells of a ``CodeMeterBank``.
+    Host arithmetic only, no device.
+
+    Per slot the rule appends the completed sub-cells of every call.  A slot that is inactive, has
+    ``n = 0``, ``bad > 0`` or a gap in its sub-cell index is reset (buffer cleared, gate closed; sub-cells
+    that come with a gap start the new buffer).  Once a slot holds ``P * (23 * words + 1)`` sub-cells it
+    is evaluated and those sub-cells are dropped: for each of the P timing phases the ``23 * words`` cell
+    values (sums of P sub-cells) have their mean removed and are correlated, signed and normalised,
+    with the mean-removed +-1 pattern of the wanted word (complemented for an inverted code), tiled
+    ``words`` times, at each of the 23 rotations; the score is the largest of the 8 x 23 values, 0 where
+    the cells have no variance, and the code is detected where the score is above ``threshold``.  A
+    detection opens the gate and clears the miss count, a miss increments it, ``hang`` misses in a row
+    close the gate.  A slot that is unused (``set_used``) has no code squelch and reads open.
+
+    ``words = 4``, ``threshold = 0.8`` and ``hang = 2`` are parameters chosen by hand on a simulation
+    (DESIGN.md 5.7o), not measurements of off-air audio."""
+
+    def __init__(self, n_channels: int, *, words: int = 4, threshold: float = 0.8, hang: int = 2):
+        K = int(n_channels)
+        if K < 1:
+            raise ValueError("at least one slot")
+        if int(words) != words or not 1 <= words <= 64:
+            raise ValueError("words must be a whole number of code words, 1 ... 64")
+        if not (math.isfinite(threshold) and 0 <= threshold < 1):
+            raise ValueError("threshold must lie in [0, 1)")
+        if int(hang) != hang or hang < 1:
+            raise ValueError("hang must be a whole number of windows, at least 1")
+        self.n_channels, self.words, self.threshold, self.hang = K, int(words), float(threshold), int(hang)
+        self.need = CODE_SUBCELLS * (CODE_WORD_BITS * self.words + 1)
+        self._buf = np.zeros((K, 2 * self.need), np.int64)
+        self._fill = np.zeros(K, np.int64)
+        self._next = np.full(K, -1, np.int64)               # the sub-cell index the buffer goes on with; -1: none
+        self._gate = np.zeros(K, bool)
+        self._misses = np.zeros(K, np.int64)
+        self._score = np.full(K, np.nan)
+        self._used = np.zeros(K, bool)
+        self._word = np.zeros(K, np.int64)
+
+    def _slot(self, k: int) -> int:
+        if not 0 <= int(k) < self.n_channels:
+            raise ValueError(f"no slot {k}")
+        return int(k)
+
+    def set_code(self, k: int, code: int, inverted: bool = False) -> None:
+        """Slot k's wanted code; the slot starts again (``reset(k)``)."""
+        k = self._slot(k)
+        word = dcs_word(code)
+        self._word[k] = word ^ 0x7FFFFF if inverted else word
+        self.set_used(k, True)
+
+    def set_used(self, k: int, used: bool) -> None:
+        """Whether slot k has a code squelch at all; the slot starts again."""
+        k = self._slot(k)
+        self._used[k] = bool(used)
+        self.reset(k)
+
+    @property
+    def open(self) -> np.ndarray:
+        """The gate per slot (bool[K]); a slot without a wanted code reads open."""
+        return self._gate | ~self._used
+
+    @property
+    def score(self) -> np.ndarray:
+        """Every slot's score of its last evaluated window (float64[K]); NaN before its first."""
+        return self._score.copy()
+
+    def reset(self, k: int | None = None) -> None:
+        """Slot k (None: every slot): buffer cleared, gate closed, no score."""
+        s = slice(None) if k is None else self._slot(k)
+        for a, v in ((self._fill, 0), (self._next, -1), (self._gate, False), (self._misses, 0), (self._score, np.nan)):
+            a[s] = v
+
+    def update(self, first, count, sums, bad, n, active=None) -> np.ndarray:
+        """One call's results as ``CodeMeterBank`` hands them out -- first[K], count[K], the sums as
+        [K, >= max count] or K arrays, bad[K], n[K] -> ``open``."""
+        K = self.n_channels
+        first, count, bad, n = (np.asarray(a, np.int64) for a in (first, count, bad, n))
+        act = np.ones(K, bool) if active is None else np.asarray(active, bool)
+        if any(a.shape != (K,) for a in (first, count, bad, n, act)) or len(sums) != K or count.min() < 0:
+            raise ValueError(f"{K} values of each expected")
+        cmax = int(count.max())
+        if not (isinstance(sums, np.ndarray) and sums.ndim == 2):
+            rows, sums = sums, np.zeros((K, cmax), np.int64)
+            for k in range(K):
+                sums[k, :count[k]] = np.asarray(rows[k], np.int64)[:count[k]]
+        if sums.shape[1] < cmax:
+            raise ValueError("fewer sums than a slot's count")
+        # every slot at once -- this runs per packet; only a slot whose window is full takes the loop below
+        live = self._used & act & (n > 0) & (bad == 0)
+        takes = live & (count > 0)
+        gone = (self._used & ~live) | (takes & (self._next >= 0) & (first != self._next))
+        if gone.any():
+            for a, v in ((self._fill, 0), (self._next, -1), (self._gate, False), (self._misses, 0),
+                         (self._score, np.nan)):
+                a[gone] = v
+        if not takes.any():
+            return self.open
+        if int(self._fill.max()) + cmax > self._buf.shape[1]:
+            grown = np.zeros((K, 2 * (int(self._fill.max()) + cmax)), np.int64)
+            grown[:, :self._buf.shape[1]] = self._buf
+            self._buf = grown
+        cols = np.arange(cmax)
+        mask = (cols[None, :] < count[:, None]) & takes[:, None]
+        slot, col = np.nonzero(mask)
+        self._buf[slot, self._fill[slot] + col] = sums[slot, col]
+        self._fill += np.where(takes, count, 0)
+        self._next = np.where(takes, first + count, self._next)
+        for k in np.flatnonzero(self._fill >= self.need):
+            fill = int(self._fill[k])
+            while fill >= self.need:
+                rho = dcs_score(self._buf[k, :self.need], int(self._word[k]), self.words)
+                fill -= self.need
+                self._buf[k, :fill] = self._buf[k, self.need:self.need + fill].copy()
+                self._score[k] = rho
+                if rho > self.threshold:
+                    self._gate[k] = True
+                    self._misses[k] = 0
+                else:
+                    self._misses[k] += 1
+                    if self._misses[k] >= self.hang:
+                        self._gate[k] = False
+            self._fill[k] = fill
+        return self.open
+
+
 # ---------------------------------------------------------------- audio FIR bank
 
 AUDIO_FIR_MAX_TAPS = _lib.RFA_AUDIO_FIR_MAX_TAPS
@@ -1802,6 +2137,16 @@ class _BankChain(_Chain):
     demodulators wrote them, the gate lags by one call, and a slot that the carrier squelch reopens
     starts tone-closed until its first window has passed.
 
+    ``code``: None (no code meter handle, nothing more enqueued), or one entry per slot: a DCS code as
+    ``dcs_parse`` takes it (``"023"``, ``"023I"``, ``0o023``), or None for a slot without code squelch,
+    which is always code-open; a slot with both a tone and a code is a ``ValueError``.  The chain then
+    owns a ``CodeMeterBank`` on the demodulators' audio rows (``code_meter``) and a ``CodeRule``, and
+    steps them in the tone meter's order: collect call j-1, step the rule (a slot is active where its
+    count in call j-1 was above 0), enqueue the meter on call j's rows with the demodulator bank's
+    counts, report call j's counts with 0 for the slots whose code gate is closed.  The audio rows stay
+    untouched, the gate lags by one call, and ``audio_filter=`` and ``pcm=`` treat a code-closed slot
+    as a tone-closed one.
+
     ``audio_filter``: None (no filter handle, no second audio buffer, nothing more enqueued), or one
     entry per slot: None (pass-through), ``"voice"`` (``voice_taps()``) or a 1-D float array of taps.
     The chain then owns an ``AudioFilterBank`` (``audio_fir``) that runs behind the demodulator bank
@@ -1826,16 +2171,18 @@ class _BankChain(_Chain):
     _reported = None           # the last call's reported counts, kept only with pcm=
     _filtered = None           # the filter's rows; the handle is self.audio_fir, present only with audio_filter=
     _audio_counts = None
+    _code = None               # the CodeRule; the meter handle is self.code_meter, present only with code=
     _tone = None               # the ToneRule; the meter handle is self.tone_meter, present only with tone=
     _afc = None                # the AfcRule; the meter handle is self.meter, present only with AFC
     _nominal = None            # (frequency, [channel frequencies]) of the user's set_frequencies
 
     def __init__(self, input_format: str, sample_rate: int, modes, rate: int, device: int, *front_args,
-                 squelch=None, afc=None, tone=None, audio_filter=None, pcm=None):
+                 squelch=None, afc=None, tone=None, audio_filter=None, pcm=None, code=None):
         import torch
 
         rule, self._afc_default_limit = _afc_rule(afc, modes, rate)
         probes = _tone_entries(tone, len(modes))
+        codes = _code_entries(code, len(modes), None if probes is None else list(tone))
         filters = _audio_filter_entries(audio_filter, len(modes))
         resampler = _pcm_entry(pcm)
         self._torch = torch
@@ -1865,6 +2212,12 @@ class _BankChain(_Chain):
                 self._tone = ToneRule(self._n_channels, AUDIO_RATE)
                 for k, f10 in enumerate(probes):
                     self._set_tone_probes(k, f10)
+            if codes is not None:
+                self.code_meter = CodeMeterBank(self._n_channels, AUDIO_RATE, device)
+                self._code = CodeRule(self._n_channels)
+                for k, entry in enumerate(codes):
+                    if entry is not None:
+                        self._code.set_code(k, *entry)
             if filters is not None:
                 self.audio_fir = AudioFilterBank(self._n_channels, device)
                 for k, taps in enumerate(filters):
@@ -1954,6 +2307,46 @@ class _BankChain(_Chain):
         m = self.tone_meter
         m._call("collect", m._sums.ctypes.data, m._n.ctypes.data)
         gate = self._tone.update(m._sums, m._n)
+        m._call("process", self._audio.data_ptr(), cap, self.demods._counts)
+        return [c if g else 0 for c, g in zip(counts, gate)]
+
+    def _code_rule(self) -> CodeRule:
+        if self._code is None:
+            raise ValueError("this chain was built without a code squelch (code=None)")
+        return self._code
+
+    @property
+    def code_open(self):
+        """The code gate per slot as of the last call (bool[K]; True for a slot without a code); None
+        without ``code=``."""
+        return None if self._code is None else self._code.open
+
+    @property
+    def code_score(self):
+        """Every slot's score of its last evaluated window (float64[K], NaN before a slot's first);
+        None without ``code=``."""
+        return None if self._code is None else self._code.score
+
+    def set_code(self, k: int, entry) -> None:
+        """Slot k's wanted DCS code as ``dcs_parse`` takes it (None: no code squelch on this slot, always
+        code-open): starts the slot's sub-cell index again and resets its rule."""
+        rule = self._code_rule()
+        k = rule._slot(k)
+        parsed = None if entry is None else dcs_parse(entry)
+        if parsed is not None and self._tone is not None and self._tone._used[k, 0]:
+            raise ValueError(f"slot {k} has a tone: a slot has a tone or a code, not both")
+        self.code_meter.break_(k)
+        if parsed is None:
+            rule.set_used(k, False)
+        else:
+            rule.set_code(k, *parsed)
+
+    def _step_code(self, counts, cap: int) -> list[int]:
+        """Collect the previous call's sub-cells, step the rule, enqueue the meter on this call's audio."""
+        m = self.code_meter
+        m._room(cap)
+        m._call("collect", *m._out())
+        gate = self._code.update(m._first, m._count, m._sums, m._bad, m._n)
         m._call("process", self._audio.data_ptr(), cap, self.demods._counts)
         return [c if g else 0 for c, g in zip(counts, gate)]
 
@@ -2050,6 +2443,8 @@ class _BankChain(_Chain):
             self.meter.set_stream(self.demods.stream)
         if self._tone is not None:
             self.tone_meter.set_stream(self.demods.stream)
+        if self._code is not None:
+            self.code_meter.set_stream(self.demods.stream)
         if hasattr(self, "audio_fir"):
             self.audio_fir.set_stream(self.demods.stream)
         if hasattr(self, "audio_rs"):
@@ -2104,6 +2499,8 @@ class _BankChain(_Chain):
                                  self._filtered.data_ptr(), cap)
         if self._tone is not None:
             counts = self._step_tone(counts, cap)
+        if self._code is not None:
+            counts = self._step_code(counts, cap)
         if self._pcm is not None:
             rs = self.audio_rs
             rs._call("process", self.audio_tensor.data_ptr(), cap, self.demods._counts, None, 0, self._pcm.data_ptr(),
@@ -2132,6 +2529,10 @@ class _BankChain(_Chain):
             self.tone_meter.close()
             del self.tone_meter
             self._tone = None
+        if self._code is not None:
+            self.code_meter.close()
+            del self.code_meter
+            self._code = None
         if hasattr(self, "audio_fir"):
             self.audio_fir.close()
             del self.audio_fir
@@ -2154,10 +2555,10 @@ class ReceiverBank(_BankChain):
     Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
 
     def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0, *, squelch=None, afc=None,
-                 tone=None, audio_filter=None, pcm=None):
+                 tone=None, audio_filter=None, pcm=None, code=None):
         self._cap_for = (None, 0)
         super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch, afc=afc, tone=tone,
-                         audio_filter=audio_filter, pcm=pcm)
+                         audio_filter=audio_filter, pcm=pcm, code=code)
 
     def _make_front(self):
         return FrontEndBank(self.input_format, self.sample_rate, self.quadrature_rate, self.n_channels, self.device,
@@ -2491,7 +2892,8 @@ class RasterReceiverBank(_BankChain):
     quadrature rate (``ValueError`` otherwise, at creation and in ``set_mode``)."""
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0,
-                 resample: bool = False, *, squelch=None, afc=None, tone=None, audio_filter=None, pcm=None):
+                 resample: bool = False, *, squelch=None, afc=None, tone=None, audio_filter=None, pcm=None,
+                 code=None):
         if afc is not None and afc is not False:
             raise ValueError("a RasterReceiverBank cannot tune: its prototype passes one raster channel per slot and "
                              "leaves no room to move; use a TunedReceiverBank for AFC")
@@ -2501,7 +2903,7 @@ class RasterReceiverBank(_BankChain):
             raise ValueError(f"{len(modes)} channels expected, got {len(channels)}")
         self._resample = bool(resample)
         super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, channels, squelch=squelch,
-                         tone=tone, audio_filter=audio_filter, pcm=pcm)
+                         tone=tone, audio_filter=audio_filter, pcm=pcm, code=code)
 
     def _make_front(self, spacing_hz: int, channels):
         make = Channelizer.for_raster_resampled if self._resample else Channelizer.for_raster
@@ -2538,14 +2940,14 @@ class TunedReceiverBank(_BankChain):
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, device: int = 0,
                  resample: bool = False, *, squelch=None, passband_hz: float | None = None, afc=None, tone=None,
-                 audio_filter=None, pcm=None):
+                 audio_filter=None, pcm=None, code=None):
         modes, rate = _common_rate(modes)
         if passband_hz is None:
             passband_hz = int(spacing_hz) / 2 + max(mode_info(m)[2] for m in modes)
         self.passband_hz = float(passband_hz)
         self._resample = bool(resample)
         super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch, afc=afc,
-                         tone=tone, audio_filter=audio_filter, pcm=pcm)
+                         tone=tone, audio_filter=audio_filter, pcm=pcm, code=code)
 
     def _make_front(self, spacing_hz: int):
         front = Channelizer.for_channels(self.input_format, self.sample_rate, spacing_hz, self.quadrature_rate,
