@@ -1057,7 +1057,15 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
                           h->variant != 1 && h->diag == 0 && !h->d_stamps && (h->ring_logrs & rfa::kRingTile) &&
                           h->stage && (((uintptr_t)in | (uintptr_t)stride) & 15) == 0 &&
                           rfa::state_fused_plan(n, (int)n_frames, h->state_chunks, h->state_fused, nullptr, nullptr);
-    const bool raise = raise_ok && h->shadow_fresh;
+    // The split (rfa::state_split, the one source of it): the state pass reads the frames from
+    // first_frame on for the EMA and takes their peaks there, so the main kernel raises only the
+    // frames below it.  Where the EMA's tail covers the whole call (first_frame 0) the raise buys
+    // nothing: the plain kernel runs and the pass is the non-raised one, which still leaves the
+    // shadow equal to the peaks.
+    bool raise = raise_ok && h->shadow_fresh;
+    const int first_frame = rfa::state_split(n, (int)n_frames, h->state_chunks, h->state_fused, h->d_ema != nullptr,
+                                             h->cfg.ema_alpha, raise, nullptr, nullptr);
+    raise = raise && first_frame > 0;
     FftLaunch a;
     a.in = (const uint8_t *)in;
     a.frame_stride = (long long)stride;
@@ -1065,7 +1073,7 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
     a.fmt = fmt;
     a.window = window;
     a.rows = state_rows;
-    if (raise) a.peaks_st = h->d_peaks_st;
+    if (raise) a.peaks_st = h->d_peaks_st, a.raise_below = first_frame;
     if (pipe) a.cus = h->pipe_fft_cus;
     if (h->d_ring) {
         a.ring = h->d_ring;
@@ -1090,7 +1098,7 @@ static int process_impl(rfa_handle *h, const void *in, size_t n_frames, size_t s
         s.part = h->d_state_part;
         s.max_chunks = h->state_chunks;
         s.fused = h->state_fused;
-        s.first_frame = (int)std::max<long long>(0, (long long)n_frames - rfa::ema_tail_frames(h->cfg.ema_alpha));
+        s.first_frame = first_frame;
         s.peaks_st = raise_ok ? h->d_peaks_st : nullptr;
         s.raised = raise;
         s.stream = state_stream;

@@ -99,7 +99,11 @@ struct FftLaunch {
     // position to every row value of the call that is above it, with integer atomics on the
     // float's bits, and the state pass folds the result into the peaks (StateLaunch::peaks_st,
     // raised).  Null: off, the kernel without the raise.
+    // raise_below: only the frames below it raise -- state_split()'s first frame: the state pass
+    // reads the frames from it on for the EMA and takes their peaks there.  The others take the
+    // plain tile stores.  In [1, n_frames] whenever peaks_st is given (0: pass no peaks_st).
     float *peaks_st = nullptr;
+    int raise_below = 0;
     // kernel B of the large-N pair (fmt == kFmtDif): S = dif_ss column residues per
     // frame; work item u is (frame u / S, residue s = u % S), input z_s at
     // in + (u * M) complex, outputs bins S q + s of an N = S * M frame; its dB rows
@@ -195,13 +199,15 @@ struct StateLaunch {
     int max_chunks = 1;
     int fused = 1;           // single-launch chunked scan (RFA_STATE_FUSED=0: partial + combine kernels)
     // The single-launch scan only (every other state kernel ignores them and reads every frame):
-    // first_frame: the EMA reads the frames from it on -- its live tail, n_frames -
-    //   ema_tail_frames(alpha), or 0; the frames before it are read for the peaks alone, and not
-    //   at all when the main kernel raised them;
+    // first_frame: the EMA reads the frames from it on -- state_split()'s first frame, which
+    //   launch_state computes itself (a raised call must pass the same value: it is the main
+    //   kernel's raise_below); the frames before it are read for the peaks alone, and not at all
+    //   when the main kernel raised them;
     // peaks_st: the peaks' shadow in the ring row's storage order (FftLaunch::peaks_st), left equal
     //   to the peaks by the fold;
-    // raised: the main kernel raised the shadow with this call's rows, so the frame loop does no
-    //   peak work and the fold takes peaks = max(peaks, shadow).
+    // raised: the main kernel raised the shadow with the rows of the frames before first_frame, so
+    //   the frame loop takes the peaks of the frames it reads (from first_frame on) and the fold
+    //   takes peaks = max(peaks, shadow, those).
     int first_frame = 0;
     float *peaks_st = nullptr;
     bool raised = false;
@@ -220,6 +226,16 @@ int ema_tail_frames(float alpha);
 // The single-launch chunked scan launch_state takes for n_frames rows of n bins (max_chunks
 // summaries, fused on): true with its chunk count and chunk length, else false
 bool state_fused_plan(int n, int n_frames, int max_chunks, int fused, int *chunks, int *chunk_len);
+// Where the single-launch scan splits a call of n_frames rows (state_fused_plan() true for it):
+// the first frame the scan's chunks read, with their count and length.  The EMA (ema: on, with
+// alpha) reads its live tail, the frames from n_frames - ema_tail_frames(alpha) on: the tail's
+// own plan, eight chunks where the tail is shorter than the smallest plan, or the whole call's
+// plan from frame 0 where n allows neither.  With the EMA off no chunk needs a row: frame 0 and
+// the whole call's plan for the peaks, or n_frames when the main kernel raised them (raised).
+// The one source of the split: a raised call's main kernel raises the frames below the result
+// (FftLaunch::raise_below) and launch_state takes the peaks of the frames from it on.
+int state_split(int n, int n_frames, int max_chunks, int fused, bool ema, float alpha, bool raised, int *chunks,
+                int *chunk_len);
 // Mean of row[first, last) for every frame (rows addressed as in StateLaunch).
 // channel mean of every frame (FftProcessor.kt:143-157); channels wider than 16384 bins are
 // summed in channel_mean_spans() pieces whose sums go to partial[n_frames][spans] first

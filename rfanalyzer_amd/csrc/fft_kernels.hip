@@ -573,8 +573,9 @@ __global__ void state_combine_kernel(StateLaunch a, int chunks) {
 // The EMA reads the frames from first_frame on (its live tail: launch_state), and the chunks
 // divide those; the result is the same function of the rows whether or not the frames before
 // them are read.  They are read for the peaks alone, a share per chunk thread -- unless RAISED:
-// the main kernel has raised the shadow peaks_st with this call's rows already, so no frame loop
-// does peak work, the frames before first_frame are not read and the fold takes the shadow.
+// the main kernel has raised the shadow peaks_st with the rows of those frames already
+// (FftLaunch::raise_below = first_frame), so they are not read and the fold takes the shadow
+// beside the chunk maxima of the frames from first_frame on, whose peaks are taken here.
 // Whenever a shadow is given the fold leaves it equal to the peaks (the main kernel compares
 // the next call's rows against it).
 template <int CH, bool RAISED = false>
@@ -595,14 +596,7 @@ __global__ void __launch_bounds__(256) state_fused_kernel(StateLaunch a, int chu
         auto step = [&](float4 x4) {
             const float xs[4] = {x4.x, x4.y, x4.z, x4.w};
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if constexpr (RAISED) {
-                    emi[k] = ema_step(emi[k], xs[k], al);
-                    b[k] = fmaf(al, xs[k] - b[k], b[k]);
-                } else {
-                    state_step(pk[k], nan[k], emi[k], b[k], xs[k], al);
-                }
-            }
+            for (int k = 0; k < 4; k++) state_step(pk[k], nan[k], emi[k], b[k], xs[k], al);
             am *= keep;
         };
         auto peak_step = [&](float4 x4) {  // a frame before the tail: the peaks alone
@@ -656,7 +650,7 @@ __global__ void __launch_bounds__(256) state_fused_kernel(StateLaunch a, int chu
             for (int cc = 0; cc < CH; cc++) {
                 const bool any = decltype(all)::value || cc * chunk_len < tail;
                 const float4 q = part[cc][i];
-                if constexpr (!RAISED) p = peak_max(p, q.x);  // (a chunk without a frame holds -inf)
+                p = peak_max(p, q.x);  // (a chunk without a frame holds -inf)
                 em = !any ? em : (!state_finite(em) || q.y < 0.0f) ? q.w : fmaf(q.y, em, q.z);
             }
         };
@@ -696,12 +690,33 @@ int ema_tail_frames(float alpha) {
     return t;
 }
 
+int state_split(int n, int n_frames, int max_chunks, int fused, bool ema, float alpha, bool raised, int *chunks,
+                int *chunk_len) {
+    int ch = 0, len = 0;
+    if (!state_fused_plan(n, n_frames, max_chunks, fused, &ch, &len)) return 0;
+    int first = !ema ? (raised ? n_frames : 0) : std::max(0, n_frames - std::min(n_frames, ema_tail_frames(alpha)));
+    if (first > 0) {
+        const int tail = n_frames - first;
+        if (!state_fused_plan(n, tail, max_chunks, fused, &ch, &len)) {
+            if (n % 128 == 0) ch = 8, len = std::max(1, (tail + 7) / 8);
+            else first = 0;  // (ch, len) of the whole call
+        }
+    }
+    if (chunks) *chunks = ch;
+    if (chunk_len) *chunk_len = len;
+    return first;
+}
+
 hipError_t launch_state(const StateLaunch &a) {
     if (a.n_frames <= 0) return hipSuccess;
     const int tpb = 256;
-    // raised peaks are folded by the single-launch scan alone
+    // raised peaks are folded by the single-launch scan alone, from the frame the main kernel
+    // stopped raising at
     if (a.raised && !(a.peaks && a.peaks_st && state_fused_plan(a.n, a.n_frames, a.max_chunks, a.fused, nullptr, nullptr) &&
-                      a.part && (a.ring_logrs & kRingTile)))
+                      a.part && (a.ring_logrs & kRingTile) &&
+                      a.first_frame == state_split(a.n, a.n_frames, a.max_chunks, a.fused, a.ema != nullptr, a.ema_alpha,
+                                                   true, nullptr, nullptr) &&
+                      a.first_frame > 0))
         return hipErrorInvalidValue;
     if (a.ring_rows > 0 && !(a.ring_logrs & kRingTile) && a.ring_logrs >= 3 && a.ring_logrs <= 5 && !kStateTileOff) {
         // column-order ring (N >= 256 K): tiled sequential update (RFA_STATE_TILE=0: A/B off)
@@ -721,16 +736,9 @@ hipError_t launch_state(const StateLaunch &a) {
         // are planned over the frames from first_frame on (eight chunks where the tail is shorter
         // than the plan's smallest scan), so the average does not depend on whether the frames
         // before it are read too -- they are for the peaks, unless the main kernel raised them
-        // (with the EMA off a raised call reads no row at all)
+        // (with the EMA off a raised call reads no row at all): state_split()
         StateLaunch b = a;
-        b.first_frame = !a.ema ? (a.raised ? a.n_frames : 0) : std::min(std::max(a.first_frame, 0), a.n_frames);
-        if (b.first_frame > 0) {
-            const int tail = a.n_frames - b.first_frame;
-            if (!state_fused_plan(a.n, tail, a.max_chunks, a.fused, &ch, &len)) {
-                if (a.n % 128 == 0) ch = 8, len = std::max(1, (tail + 7) / 8);
-                else b.first_frame = 0;  // (ch, len) of the whole call
-            }
-        }
+        b.first_frame = state_split(a.n, a.n_frames, a.max_chunks, a.fused, a.ema != nullptr, a.ema_alpha, a.raised, &ch, &len);
         auto k = a.raised ? (ch == 32 ? state_fused_kernel<32, true> : ch == 16 ? state_fused_kernel<16, true>
                                                                                  : state_fused_kernel<8, true>)
                           : (ch == 32 ? state_fused_kernel<32> : ch == 16 ? state_fused_kernel<16> : state_fused_kernel<8>);

@@ -52,6 +52,11 @@ namespace rfa {
 #define RFA_PKR_WIN_UPFRONT 4  // ... of the peak-raise kernel, whose epilogue holds the 32 shadow values beside the
                                // 32 row values: 16 spill (72 B of scratch), 12: 60 B, 8: 20 B, 4: none
 #endif
+#ifndef RFA_PKR_TWO_BODIES
+#define RFA_PKR_TWO_BODIES 0  // A/B: the peak-raise kernel's item body instantiated twice per residue, the raising one
+                              // for a workgroup's items below raise_below, then the plain one (RFA_WIN_UPFRONT
+                              // pairs, no shadow registers); profiles/raise_split/two_bodies_ab.txt
+#endif
 #ifndef RFA_WIDE_KR1
 #define RFA_WIDE_KR1 0
 #endif
@@ -580,8 +585,9 @@ __device__ __forceinline__ void stage_half_own(const void *src, float2 *buf) {
 // STG: raw input staged through LDS by LDS-DMA one work item ahead (8/16-bit
 // formats, one sub-FFT per workgroup, frame fits the exchange buffer; the
 // host launches a persistent grid and checks 16-byte alignment).
-// PKR (peak raise; the staged two-residue 8-bit kernels only): every item raises FftLaunch::peaks_st
-// to its row values where they are higher (raise_peak below).
+// PKR (peak raise; the staged two-residue 8-bit kernels only): every item of a frame below
+// FftLaunch::raise_below raises FftLaunch::peaks_st to its row values where they are higher
+// (raise_peak below); the items of the other frames store their tiles and no more.
 template <int LOGM, int PT, int RS, int FMT, bool COMPLEX_OUT, int DIAG = 0, bool STG = false, bool PKR = false>
 #ifndef RFA_WIDE_WPE
 #define RFA_WIDE_WPE 0  // A/B builds: waves per EU the wide kernels are compiled for (0: the launch bound's 4)
@@ -760,8 +766,11 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
     };
 
 #if RFA_RES_HOIST
-    auto body = [&]<int RF>(int u, int unext) {  // RF >= 0: every item of this loop is residue RF
+    // RZ: the body with the peak-raise epilogue (and its RFA_PKR_WIN_UPFRONT window pairs)
+    auto body = [&]<int RF, bool RZ = PKR>(int u, int unext) {  // RF >= 0: every item of this loop is residue RF
 #else
+    constexpr bool RZ = PKR;
+    constexpr int RF = -1;
     auto body = [&](int u, int unext) {
 #endif
         stamp(u, 0);
@@ -855,7 +864,7 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
                 ((r == Rs ? prestage<LOGM, PT, RS, FMT, Rs, STG, (DIAG & 16) != 0, QST ? QN : JS,
 #endif
                                      RS == 2 && Rs == 1 && FMT <= 2 && (DIAG & 16) == 0, QCH,
-                                     PKR ? RFA_PKR_WIN_UPFRONT : RFA_WIN_UPFRONT>(
+                                     RZ ? RFA_PKR_WIN_UPFRONT : RFA_WIN_UPFRONT>(
                                 v, a.window_il, a.wide_tw, in_rs, tid, planar, lraw, a.window_cw)
                           : void()), ...);
             }(std::make_integer_sequence<int, RS>{});
@@ -898,7 +907,7 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
         }
 
         if (!active) return;
-        if constexpr (PKR) {
+        if constexpr (RZ) {
             // ---- epilogue of the peak-raise kernel: the tile stores of the form below (the launch
             // checks that every frame goes to the tiled ring and that no caller rows are asked for)
             // and the row values against the shadow, whose loads fly under the dB arithmetic
@@ -909,6 +918,21 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
             float *blk = a.peaks_st + (size_t)r * M;
             const rsrc_t p_rs = make_rsrc(blk, M * 4);
             const rsrc_t ring_rs = make_rsrc(a.ring + (size_t)rr * n + (size_t)r * M, M * 4);
+            // a frame from raise_below on (uniform per item): the state pass reads it for the EMA
+            // and takes its peaks there, so it gets the plain tile stores
+            if (!(RFA_PKR_TWO_BODIES && RF >= 0) && frame >= a.raise_below) {
+#pragma unroll
+                for (int j = 0; j < PT / 4; j++) {
+                    float d[4];
+#pragma unroll
+                    for (int e = 0; e < 4; e++) d[e] = db_unscaled(v[(4 * j + e + 16) & 31], db_off);  // nativedsp.cpp:73-78
+                    if constexpr (RFA_RING_SC1) buf_store_f32x4(d[0], d[1], d[2], d[3], ring_rs, tp * 4, j * 1024);
+                    else buf_store_f32x4_wb(d[0], d[1], d[2], d[3], ring_rs, tp * 4, j * 1024);
+                }
+                pending_st = PT / 4;
+                stamp(u, 6);
+                return;
+            }
             pk4v shadow[PT / 4];
 #pragma unroll
             for (int j = 0; j < PT / 4; j++)
@@ -1085,7 +1109,24 @@ __global__ void __launch_bounds__((WGeo<LOGM, PT>::THREADS), (PT == 64 ? 2 : 4))
     };
 #if RFA_RES_HOIST
     auto loop = [&]<int RF>() {
-        for (int u = u0; u < items; it_count++) {
+        int u = u0;
+        if constexpr (PKR && RFA_PKR_TWO_BODIES && RF >= 0) {
+            // a workgroup's frames rise with its items (the grid is a multiple of 8 RS): the raising
+            // body while they are below raise_below, then the plain one.  Both leave pending_st and
+            // the next item's staged halves alike, so the hand-over item waits as any other.
+            for (; u < items && frame_of(u) < a.raise_below; it_count++) {
+                const int un = next_item(u);
+                body.template operator()<RF, true>(u, un);
+                u = un;
+            }
+            for (; u < items; it_count++) {
+                const int un = next_item(u);
+                body.template operator()<RF, false>(u, un);
+                u = un;
+            }
+            return;
+        }
+        for (; u < items; it_count++) {
             const int un = next_item(u);
             body.template operator()<RF>(u, un);
             u = un;
@@ -1120,7 +1161,7 @@ static hipError_t launch_wide_one(const FftLaunch &a) {
     // peak raise: only the kernel that has it may be asked for it, and only for the stores it
     // taps (every frame into the tiled ring, no caller rows)
     if (a.peaks_st && !(PKR && a.ring && (a.ring_logrs & kRingTile) && !a.rows && a.ring_first == 0 &&
-                        a.n_frames <= a.ring_rows))
+                        a.n_frames <= a.ring_rows && a.raise_below > 0 && a.raise_below <= a.n_frames))
         return hipErrorInvalidValue;
     const size_t lds = (size_t)G::LDS_BYTES;
     if (!a.wide_tw) return hipErrorInvalidValue;
