@@ -40,6 +40,7 @@
  *   (extension) DCS sub-cell sums of every bank slot's audio rfa_code_*() (code meter bank, below)
  *   (extension) a real FIR on every bank slot's audio      rfa_audio_fir_*() (audio FIR bank, below)
  *   (extension) every bank slot's audio to 8 / 16 kHz PCM  rfa_audio_rs_*() (audio resampler bank, below)
+ *   (extension) recursive sections on every slot's audio   rfa_audio_iir_*() (audio IIR bank, below)
  *   (north-star extension) exponential average             rfa_get_ema()
  *     idiom of database/GlobalPerformanceData.kt:44-50
  *
@@ -1442,6 +1443,115 @@ RFA_API int rfa_audio_rs_process_host(rfa_audio_rs *s, const float *in, size_t i
 RFA_API int rfa_audio_rs_set_stream(rfa_audio_rs *s, void *stream);
 RFA_API int rfa_audio_rs_get_stream(const rfa_audio_rs *s, void **stream);
 RFA_API int rfa_audio_rs_synchronize(rfa_audio_rs *s);
+
+/* ---------------------------------------------------------------------------
+ * Audio IIR bank (extension): second-order recursive sections on every bank slot's audio row
+ *
+ * What an NFM receiver ends in, a 6 dB / octave de-emphasis, and a tone strip that a packet
+ * can afford: an 8th-order Chebyshev II high-pass (demod.tone_strip_sections) in place of
+ * the 1309-tap FIR.  The reference filters no audio behind its demodulator and has no
+ * recursive filter: no entry of this section has a counterpart there.  The stage is defined
+ * by the text below and checked against its restatement in numpy (tests/audio_iir_ref.py),
+ * bit for bit.
+ *
+ * Slot k has S sections, 0 <= S <= RFA_AUDIO_IIR_MAX_SECTIONS, each five float32
+ * coefficients (b0, b1, b2, a1, a2) with a0 = 1; a first-order section has b2 = a2 = 0.
+ * S = 0 copies the row bit for bit, NaN payloads included.  Section q's input is section
+ * q-1's output, section 0's the row.  Every product and every sum below is rounded to
+ * float32, in the written order, nothing contracted.
+ *
+ * B = RFA_AUDIO_IIR_BLOCK.  A slot counts the samples it has consumed since its last reset
+ * or set_sections, a = 0, 1, ...; sample a lies in block a div B at offset i = a mod B.
+ * One step (transposed direct form II) with state (z1, z2) and input u:
+ *     v = (b0*u) + z1;   z1' = ((b1*u) - (a1*v)) + z2;   z2' = (b2*u) - (a2*v)
+ * Per section and block j with block-start state s0_j (two floats, s0_0 = (0, 0)):
+ *   zero-state response: zs[i] and the running state z are that step started from
+ *     z = (0, 0) at i = 0 and run over the block's inputs;
+ *   output:      y[i] = zs[i] + ((G[i][0]*s0_j[0]) + (G[i][1]*s0_j[1]))
+ *   next block:  s0_{j+1}[r] = ((P[r][0]*s0_j[0]) + (P[r][1]*s0_j[1])) + z_end[r], r = 0, 1,
+ *     z_end being z after the block's B-th step.
+ * Tables per section, computed in double from the float32 coefficients widened and rounded
+ * once to float32: A = [[-a1, 1], [-a2, 0]], R_0 = I, R_{i+1} = R_i A with every element
+ * (x0*A0c) + (x1*A1c) in that order; G[i] is the first row of R_i, i = 0 ... B-1, P = R_B.
+ *
+ * Between calls a slot carries, per section, s0 and the running z of its incomplete block,
+ * and a mod B.  A call that ends inside a block leaves these and the next call goes on from
+ * them, so a row cut into calls anywhere gives the bits of the row given whole.  A
+ * non-finite input makes the slot's state non-finite from its block on, until the slot is
+ * reset; other slots are untouched.
+ *
+ * One launch per call whatever n_channels: one workgroup per slot, which walks the row in
+ * chunks of RFA_AUDIO_IIR_CHUNK_BLOCKS blocks staged in LDS.  A slot with n = 0 keeps
+ * everything; a call whose counts are all 0 launches nothing.
+ * ------------------------------------------------------------------------ */
+typedef struct rfa_audio_iir rfa_audio_iir;
+
+#define RFA_AUDIO_IIR_MAX_CHANNELS 1024        /* n_channels above this: RFA_ERR_INVALID */
+#define RFA_AUDIO_IIR_MAX_SECTIONS 8
+#define RFA_AUDIO_IIR_BLOCK 128                /* B */
+#define RFA_AUDIO_IIR_CHUNK_BLOCKS 256         /* blocks a workgroup stages at a time, one lane each */
+/* rfa_audio_iir_plan: the path a slot takes */
+#define RFA_AUDIO_IIR_PATH_NONE 0              /* n = 0: the slot's workgroup returns at once */
+#define RFA_AUDIO_IIR_PATH_COPY 1              /* no sections: bitwise copy */
+#define RFA_AUDIO_IIR_PATH_BLOCKED 2           /* the blocked recurrence */
+#define RFA_AUDIO_IIR_PLAN_FIELDS 6            /* B, blocks per chunk, lds_bytes, path, chunks, blocks touched */
+
+/* Host only, no device, no counterpart in the reference: the library's own tables of a section
+ * with these a1, a2: G[RFA_AUDIO_IIR_BLOCK][2] and P[4] = P[0][0], P[0][1], P[1][0], P[1][1].
+ * RFA_ERR_INVALID, nothing written: a1 or a2 not finite or outside the stability triangle
+ * (|a2| < 1 and |a1| < 1 + a2), or a NULL pointer. */
+RFA_API int rfa_audio_iir_tables(float a1, float a2, float *G, float *P);
+/* Host only, no counterpart in the reference: what a call of one slot with num_sections sections,
+ * n samples and a mod B = a_mod_B runs: plan[0] RFA_AUDIO_IIR_BLOCK, [1] RFA_AUDIO_IIR_CHUNK_BLOCKS,
+ * [2] the launch's dynamic LDS bytes (0 on NONE and COPY; above 64 KiB for a full chunk: the
+ * create entry raises the kernel's limit), [3] the path, [4] the chunks the workgroup walks
+ * (0 on NONE and COPY), [5] the blocks the call touches, ceil((a_mod_B + n) / B).
+ * RFA_ERR_INVALID for num_sections outside 0 ... RFA_AUDIO_IIR_MAX_SECTIONS, a_mod_B outside
+ * 0 ... B-1, n above 2^36 or NULL. */
+RFA_API int rfa_audio_iir_plan(int32_t num_sections, size_t n, int32_t a_mod_B, int32_t *plan);
+/* Host only, no counterpart in the reference: *next = (a_mod_B + n) mod B, a slot's offset in its
+ * block after a call of n samples.  RFA_ERR_INVALID as rfa_audio_iir_plan. */
+RFA_API int rfa_audio_iir_carry_after(size_t n, int32_t a_mod_B, int32_t *next);
+
+/* 1 <= n_channels <= RFA_AUDIO_IIR_MAX_CHANNELS; arguments are checked before the device is
+ * looked for.  Every slot starts as a pass-through with a zero carry.  No counterpart in the
+ * reference, as for every entry below. */
+RFA_API int rfa_audio_iir_create(int device, int32_t n_channels, rfa_audio_iir **out);
+RFA_API int rfa_audio_iir_destroy(rfa_audio_iir *f);
+RFA_API const char *rfa_audio_iir_last_error(const rfa_audio_iir *f);
+RFA_API int rfa_audio_iir_get_channels(const rfa_audio_iir *f, int32_t *n_channels);
+/* Slot k's sections from the next call on: coeffs[num_sections][5] as (b0, b1, b2, a1, a2);
+ * num_sections = 0 is the pass-through and coeffs may then be NULL.  The slot's carry is zeroed
+ * and its block grid starts again at the next sample.  A coefficient that is not finite or a
+ * section outside the stability triangle (|a2| < 1 and |a1| < 1 + a2) is RFA_ERR_INVALID and
+ * changes nothing.  The tables are uploaded on the handle's stream behind every call enqueued
+ * so far, through one pinned stage, as rfa_audio_fir_set_taps uploads taps.  "Changes nothing"
+ * covers argument errors: after RFA_ERR_HIP the slot's tables and carry on the device are
+ * undefined until a set_sections for that slot succeeds (get_sections still reports the old ones). */
+RFA_API int rfa_audio_iir_set_sections(rfa_audio_iir *f, int32_t k, const float *coeffs, int32_t num_sections);
+/* *num_sections is slot k's S.  coeffs NULL asks for the count alone; otherwise capacity, in
+ * sections, must hold them: below S it is RFA_ERR_INVALID with *num_sections set and nothing
+ * copied. */
+RFA_API int rfa_audio_iir_get_sections(const rfa_audio_iir *f, int32_t k, float *coeffs, size_t capacity,
+                                       int32_t *num_sections);
+/* Slot k's carry (k = -1: every slot's) to zeros, ordered on the stream, and its block grid to
+ * the next sample; the sections stay. */
+RFA_API int rfa_audio_iir_reset(rfa_audio_iir *f, int32_t k);
+/* Device rows in and out, in_stride / out_stride floats apart, host counts n_audio[n_channels]
+ * (what rfa_demod_bank_process returns).  Asynchronous on the handle's stream: the call's
+ * records (counts, section counts, offsets) go through a ring of pinned entries guarded by
+ * events, then one launch.  A steady-state call allocates nothing and waits for nothing.
+ * RFA_ERR_INVALID, nothing consumed: a count above either stride where n_channels > 1, a NULL
+ * row or count array with any count > 0, input and output ranges that overlap. */
+RFA_API int rfa_audio_iir_process(rfa_audio_iir *f, const float *in, size_t in_stride, const size_t *n_audio,
+                                  float *out, size_t out_stride);
+/* rfa_audio_iir_process with host rows: synchronous. */
+RFA_API int rfa_audio_iir_process_host(rfa_audio_iir *f, const float *in, size_t in_stride, const size_t *n_audio,
+                                       float *out, size_t out_stride);
+/* As rfa_ddc_set_stream / _get_stream / _synchronize. */
+RFA_API int rfa_audio_iir_set_stream(rfa_audio_iir *f, void *stream);
+RFA_API int rfa_audio_iir_get_stream(const rfa_audio_iir *f, void **stream);
+RFA_API int rfa_audio_iir_synchronize(rfa_audio_iir *f);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,8 @@ reference's interfaces for this path:
     demod.Demodulator          analyzer/Demodulator.kt + AudioSink.java: AM/FM/SSB/CW to 48 kHz audio
     demod.Receiver             FrontEnd chained into Demodulator, raw IQ bytes to audio
     demod.AudioFilterBank      (extension) a real FIR per bank slot on the audio rows; demod.voice_taps
+    demod.AudioIirBank         (extension) recursive sections per bank slot on the audio rows: de-emphasis, tone strip;
+                               demod.deemphasis_sections, demod.tone_strip_sections, audio_iir= on the bank chains
     demod.AudioResamplerBank   (extension) every bank slot's audio by L / D to 8 / 16 kHz s16 PCM; demod.resampler_taps,
                                pcm= on the bank chains, recording.AudioLogWriter
     scheduler.Scheduler       analyzer/Scheduler.kt packet fan-out

@@ -42,6 +42,12 @@ RFA_AUDIO_RS_HISTORY = 4095
 RFA_AUDIO_RS_MAX_TILE = 1024
 RFA_AUDIO_RS_PATHS = ("none", "convert", "decimate", "polyphase")   # RFA_AUDIO_RS_PATH_* in order
 RFA_AUDIO_RS_PLAN_FIELDS = 5
+RFA_AUDIO_IIR_MAX_CHANNELS = 1024
+RFA_AUDIO_IIR_MAX_SECTIONS = 8
+RFA_AUDIO_IIR_BLOCK = 128
+RFA_AUDIO_IIR_CHUNK_BLOCKS = 256
+RFA_AUDIO_IIR_PATHS = ("none", "copy", "blocked")   # RFA_AUDIO_IIR_PATH_* in order
+RFA_AUDIO_IIR_PLAN_FIELDS = 6
 
 WINDOWS = {"blackman": 0, "hann": 1, "none": 2}
 FORMATS = {"s8": 0, "u8": 1, "s16": 2, "f32": 3, "f32p": 4}
@@ -410,6 +416,24 @@ def _declare(lib: ctypes.CDLL) -> None:
         "rfa_audio_rs_set_stream": (ctypes.c_int, [_h, _vp]),
         "rfa_audio_rs_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
         "rfa_audio_rs_synchronize": (ctypes.c_int, [_h]),
+        # audio IIR bank: recursive sections per slot on the audio rows (rfanalyzer_amd/csrc/audio_iir.hip)
+        "rfa_audio_iir_tables": (ctypes.c_int, [ctypes.c_float, ctypes.c_float, _fp, _fp]),
+        "rfa_audio_iir_plan": (ctypes.c_int, [ctypes.c_int32, ctypes.c_size_t, ctypes.c_int32,
+                                              ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_iir_carry_after": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_iir_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, ctypes.POINTER(_h)]),
+        "rfa_audio_iir_destroy": (ctypes.c_int, [_h]),
+        "rfa_audio_iir_last_error": (ctypes.c_char_p, [_h]),
+        "rfa_audio_iir_get_channels": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_iir_set_sections": (ctypes.c_int, [_h, ctypes.c_int32, _fp, ctypes.c_int32]),
+        "rfa_audio_iir_get_sections": (ctypes.c_int, [_h, ctypes.c_int32, _fp, ctypes.c_size_t,
+                                                      ctypes.POINTER(ctypes.c_int32)]),
+        "rfa_audio_iir_reset": (ctypes.c_int, [_h, ctypes.c_int32]),
+        "rfa_audio_iir_process": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t]),
+        "rfa_audio_iir_process_host": (ctypes.c_int, [_h, _vp, ctypes.c_size_t, _vp, _vp, ctypes.c_size_t]),
+        "rfa_audio_iir_set_stream": (ctypes.c_int, [_h, _vp]),
+        "rfa_audio_iir_get_stream": (ctypes.c_int, [_h, ctypes.POINTER(_vp)]),
+        "rfa_audio_iir_synchronize": (ctypes.c_int, [_h]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -61,6 +61,13 @@ slot's audio row resampled by one rational ratio L / D through one prototype FIR
 PCM, float32 or both, one launch per call; ``resampler_taps`` designs the prototype, a bank chain
 built with ``pcm=8000`` leaves the PCM in ``pcm_tensor`` and hands it out through ``pcm()``, and
 ``recording.AudioLogWriter`` writes one WAV per slot.  The reference has no counterpart.
+
+``AudioIirBank`` is a cascade of up to 8 second-order recursive sections on every slot's audio row
+(``rfa_audio_iir_*``): a blocked recurrence that a row cut into calls anywhere reproduces to the bit,
+one launch per call; ``deemphasis_sections`` is an NFM receiver's 6 dB / octave de-emphasis,
+``tone_strip_sections`` the 8th-order Chebyshev II high-pass that takes a CTCSS tone out of the voice
+(DESIGN.md 5.7p has its measured cost next to the FIR's), and a bank chain built with ``audio_iir=`` runs it directly behind the
+demodulators.  The reference has no counterpart.
 """
 from __future__ import annotations
 
@@ -1747,6 +1754,217 @@ class AudioFilterBank(_Handle):
         return [out[k, :c].copy() for k, c in enumerate(counts)]
 
 
+# ---------------------------------------------------------------- audio IIR bank
+
+AUDIO_IIR_MAX_SECTIONS = _lib.RFA_AUDIO_IIR_MAX_SECTIONS
+AUDIO_IIR_BLOCK = _lib.RFA_AUDIO_IIR_BLOCK
+AUDIO_IIR_PLAN_FIELDS = ("block", "chunk_blocks", "lds_bytes", "path", "chunks", "blocks")   # rfa_audio_iir_plan order
+AUDIO_IIR_NAMES = ("deemphasis", "voice", "voice+deemphasis")
+
+
+def _bilinear_highpass(c0: float, c1: float, wz2: float, K: float) -> list[float]:
+    """(s^2 + wz2) / (s^2 + c1 s + c0) under s = (1 - z^-1) / (K (1 + z^-1)), a0 = 1."""
+    a0 = 1.0 + c1 * K + c0 * K * K
+    n0 = 1.0 + wz2 * K * K
+    return [n0 / a0, (2.0 * wz2 * K * K - 2.0) / a0, n0 / a0, (2.0 * c0 * K * K - 2.0) / a0,
+            (1.0 - c1 * K + c0 * K * K) / a0]
+
+
+def _bilinear_highpass_first(sigma: float, K: float) -> list[float]:
+    """s / (s + sigma) under the same substitution, a0 = 1."""
+    a0 = 1.0 + sigma * K
+    return [1.0 / a0, -1.0 / a0, 0.0, (sigma * K - 1.0) / a0, 0.0]
+
+
+def _check_design(edge_hz: float, order: int, rate: float) -> None:
+    if not (math.isfinite(rate) and rate > 0 and math.isfinite(edge_hz) and 0.0 < edge_hz < rate / 2):
+        raise ValueError("the edge must lie between 0 and half the rate")
+    if not 1 <= order <= 2 * AUDIO_IIR_MAX_SECTIONS:
+        raise ValueError(f"order outside 1 ... {2 * AUDIO_IIR_MAX_SECTIONS}")
+
+
+def deemphasis_sections(tau: float = 750e-6, rate: float = AUDIO_RATE) -> np.ndarray:
+    """The one-pole de-emphasis of an NFM receiver as a float32 ``[1, 5]`` section: p = exp(-1 / (tau rate)),
+    b0 = 1 - p, a1 = -p: unit gain at DC, -3 dB at 1 / (2 pi tau), 6 dB / octave above.  Host only."""
+    tau, rate = float(tau), float(rate)
+    if not (math.isfinite(tau) and tau > 0 and math.isfinite(rate) and rate > 0):
+        raise ValueError("tau and rate must be positive")
+    p = math.exp(-1.0 / (tau * rate))
+    return np.array([[1.0 - p, 0.0, 0.0, -p, 0.0]], np.float32)
+
+
+def tone_strip_sections(stop_hz: float = 255.0, attenuation_db: float = 40.0, order: int = 8,
+                        rate: float = AUDIO_RATE) -> np.ndarray:
+    """The high-pass that takes a CTCSS tone out of the voice as float32 ``[ceil(order / 2), 5]`` sections: a
+    Chebyshev II design in closed form, at most ``-attenuation_db`` from DC to ``stop_hz`` and monotonic
+    above.  With eps = 1 / sqrt(10^(A / 10) - 1), mu = asinh(1 / eps) / order and theta_k = (2k - 1) pi /
+    (2 order), the analog pair k has zeros +-j cos(theta_k) and poles -sinh(mu) sin(theta_k) +- j cosh(mu)
+    cos(theta_k); s = (1 - z^-1) / (K (1 + z^-1)) with K = tan(pi stop / rate) maps it, normalised to
+    a0 = 1.  At the defaults: -40.0 dB at 255 Hz, -0.96 dB at 330 Hz, -0.01 dB at 400 Hz, pole radii
+    0.977 ... 0.9954.  Host only."""
+    stop_hz, attenuation_db, order, rate = float(stop_hz), float(attenuation_db), int(order), float(rate)
+    _check_design(stop_hz, order, rate)
+    if not (math.isfinite(attenuation_db) and attenuation_db > 0):
+        raise ValueError("attenuation_db must be positive")
+    eps = 1.0 / math.sqrt(10.0 ** (attenuation_db / 10.0) - 1.0)
+    mu = math.asinh(1.0 / eps) / order
+    K = math.tan(math.pi * stop_hz / rate)
+    out = []
+    for k in range(1, order // 2 + 1):
+        th = (2 * k - 1) * math.pi / (2 * order)
+        re, im = -math.sinh(mu) * math.sin(th), math.cosh(mu) * math.cos(th)
+        out.append(_bilinear_highpass(re * re + im * im, -2.0 * re, math.cos(th) ** 2, K))
+    if order % 2:
+        out.append(_bilinear_highpass_first(math.sinh(mu), K))
+    return np.array(out, np.float32)
+
+
+def highpass_sections(cutoff_hz: float, order: int, rate: float = AUDIO_RATE) -> np.ndarray:
+    """A Butterworth high-pass of ``order`` with its -3 dB point at ``cutoff_hz`` as float32
+    ``[ceil(order / 2), 5]`` sections, by the same bilinear substitution.  Host only."""
+    cutoff_hz, order, rate = float(cutoff_hz), int(order), float(rate)
+    _check_design(cutoff_hz, order, rate)
+    K = math.tan(math.pi * cutoff_hz / rate)
+    out = [_bilinear_highpass(1.0, 2.0 * math.sin((2 * k - 1) * math.pi / (2 * order)), 0.0, K)
+           for k in range(1, order // 2 + 1)]
+    if order % 2:
+        out.append(_bilinear_highpass_first(1.0, K))
+    return np.array(out, np.float32)
+
+
+def iir_response(sections, hz, rate: float = AUDIO_RATE):
+    """The cascade's response in dB at ``hz`` (a number or an array), from the coefficients as given,
+    in float64.  Host only."""
+    sec = np.asarray(sections, np.float64).reshape(-1, 5)
+    z1 = np.exp(-2j * np.pi * np.asarray(hz, np.float64) / float(rate))
+    h = np.ones_like(z1)
+    for b0, b1, b2, a1, a2 in sec:
+        h = h * (b0 + b1 * z1 + b2 * z1 * z1) / (1.0 + a1 * z1 + a2 * z1 * z1)
+    with np.errstate(divide="ignore"):
+        db = 20.0 * np.log10(np.abs(h))
+    return float(db) if db.ndim == 0 else db
+
+
+@functools.lru_cache(maxsize=4)
+def _named_sections(name: str) -> np.ndarray:
+    parts = {"deemphasis": (deemphasis_sections,), "voice": (tone_strip_sections,),
+             "voice+deemphasis": (tone_strip_sections, deemphasis_sections)}[name]
+    sec = np.concatenate([f() for f in parts])
+    sec.setflags(write=False)
+    return sec
+
+
+def _audio_iir_sections(entry):
+    """One slot's ``audio_iir`` entry -> None (pass-through) or its float32 ``[S, 5]`` sections.  Host only."""
+    what = "an audio IIR entry is None, 'deemphasis', 'voice', 'voice+deemphasis' or an [S, 5] array of sections"
+    if entry is None:
+        return None
+    if isinstance(entry, str):
+        if entry not in AUDIO_IIR_NAMES:
+            raise ValueError(f"audio IIR {entry!r}: the named ones are {AUDIO_IIR_NAMES}")
+        return _named_sections(entry)
+    if isinstance(entry, (bool, bytes, int, float)) or not hasattr(entry, "__len__"):
+        raise ValueError(what)
+    try:
+        sec = np.asarray(entry, np.float32)
+    except (TypeError, ValueError) as e:
+        raise ValueError(what) from e
+    if sec.size == 0:
+        return None
+    if sec.ndim != 2 or sec.shape[1] != 5 or sec.shape[0] > AUDIO_IIR_MAX_SECTIONS or not np.isfinite(sec).all():
+        raise ValueError(f"sections must be [S, 5], finite, S at most {AUDIO_IIR_MAX_SECTIONS}")
+    a1, a2 = sec[:, 3].astype(np.float64), sec[:, 4].astype(np.float64)
+    if not ((np.abs(a2) < 1.0) & (np.abs(a1) < 1.0 + a2)).all():
+        raise ValueError("a section's poles are not inside the unit circle (|a2| < 1 and |a1| < 1 + a2)")
+    return np.ascontiguousarray(sec)
+
+
+def _audio_iir_entries(audio_iir, n_channels: int):
+    """The ``audio_iir=`` keyword of a bank chain -> None or every slot's sections (None: pass-through).
+    Host only: a wrong entry count or type raises before any device work."""
+    if audio_iir is None:
+        return None
+    if isinstance(audio_iir, (bool, str, bytes, int, float)) or not hasattr(audio_iir, "__iter__"):
+        raise ValueError("audio_iir must be None or one entry per slot (None, a name or an [S, 5] array)")
+    entries = list(audio_iir)
+    if len(entries) != n_channels:
+        raise ValueError(f"{n_channels} audio IIR entries expected, got {len(entries)}")
+    return [_audio_iir_sections(e) for e in entries]
+
+
+def audio_iir_tables(a1: float, a2: float):
+    """The library's own tables of a section with these a1, a2 (``rfa_audio_iir_tables``): float32 ``G[128, 2]``
+    and ``P[2, 2]``.  Host only."""
+    G, P = np.empty((AUDIO_IIR_BLOCK, 2), np.float32), np.empty((2, 2), np.float32)
+    _lib.check(_lib.lib().rfa_audio_iir_tables(float(a1), float(a2), G.ctypes.data_as(_lib._fp),
+                                               P.ctypes.data_as(_lib._fp)), "rfa_audio_iir_tables")
+    return G, P
+
+
+def audio_iir_plan(num_sections: int, n: int, a_mod_b: int = 0) -> dict:
+    """What a call of one slot with ``num_sections`` sections and ``n`` samples, ``a_mod_b`` samples into a
+    block, runs (``rfa_audio_iir_plan``): ``block``, ``chunk_blocks``, ``lds_bytes``, ``path`` ("none", "copy",
+    "blocked"), ``chunks`` and ``blocks`` (touched).  Host only."""
+    out = (ctypes.c_int32 * _lib.RFA_AUDIO_IIR_PLAN_FIELDS)()
+    _lib.check(_lib.lib().rfa_audio_iir_plan(int(num_sections), int(n), int(a_mod_b), out), "rfa_audio_iir_plan")
+    plan = dict(zip(AUDIO_IIR_PLAN_FIELDS, (int(v) for v in out)))
+    plan["path"] = _lib.RFA_AUDIO_IIR_PATHS[plan["path"]]
+    return plan
+
+
+def audio_iir_carry_after(n: int, a_mod_b: int) -> int:
+    """(a_mod_b + n) mod 128 (``rfa_audio_iir_carry_after``).  Host only."""
+    nxt = ctypes.c_int32(0)
+    _lib.check(_lib.lib().rfa_audio_iir_carry_after(int(n), int(a_mod_b), ctypes.byref(nxt)), "rfa_audio_iir_carry_after")
+    return nxt.value
+
+
+class AudioIirBank(_Handle):
+    """Up to 8 second-order recursive sections on each of ``n_channels`` audio rows (``rfa_audio_iir_*``,
+    ``rfanalyzer_amd/csrc/audio_iir.hip``): every slot has its own sections (none: a bitwise
+    pass-through), its own carried state on the device and its own count per call.  The recurrence is
+    blocked -- 128-sample blocks, each the zero-state response plus the block-start state's zero-input
+    response (include/rfa.h has the definition) -- so the blocks run in parallel and a row cut into
+    calls anywhere gives the bits of the row given whole.  One launch per call whatever the slot count;
+    ``process_device`` is asynchronous on the handle's stream."""
+
+    _prefix = "rfa_audio_iir"
+
+    def __init__(self, n_channels: int, device: int = 0):
+        self.n_channels = int(n_channels)
+        self._create("rfa_audio_iir_create", device, self.n_channels)
+
+    def set_sections(self, k: int, sections) -> None:
+        """Slot k's sections from the next call on (None or empty: pass-through); its carry is zeroed."""
+        sec = None if sections is None else np.ascontiguousarray(sections, np.float32)
+        if sec is None or sec.size == 0:
+            self._call("set_sections", int(k), None, 0)
+            return
+        if sec.ndim != 2 or sec.shape[1] != 5:
+            raise ValueError("sections must be [S, 5]")
+        self._call("set_sections", int(k), sec.ctypes.data_as(_lib._fp), sec.shape[0])
+
+    def sections(self, k: int) -> np.ndarray:
+        n = ctypes.c_int32(0)
+        self._call("get_sections", int(k), None, 0, ctypes.byref(n))
+        sec = np.empty((n.value, 5), np.float32)
+        self._call("get_sections", int(k), sec.ctypes.data_as(_lib._fp), n.value, ctypes.byref(n))
+        return sec
+
+    def reset(self, k: int | None = None) -> None:
+        """Slot k's carry (None: every slot's) to zeros; the sections stay."""
+        self._call("reset", -1 if k is None else int(k))
+
+    @staticmethod
+    def plan(num_sections: int, n: int, a_mod_b: int = 0) -> dict:
+        return audio_iir_plan(num_sections, n, a_mod_b)
+
+    _count_array = AudioFilterBank._count_array
+    process_device = AudioFilterBank.process_device
+    process_tensor = AudioFilterBank.process_tensor
+    process = AudioFilterBank.process
+
+
 # ---------------------------------------------------------------- audio resampler bank
 
 AUDIO_RS_MAX_L = _lib.RFA_AUDIO_RS_MAX_L
@@ -2147,13 +2365,23 @@ class _BankChain(_Chain):
     untouched, the gate lags by one call, and ``audio_filter=`` and ``pcm=`` treat a code-closed slot
     as a tone-closed one.
 
+    ``audio_iir``: None (no handle, no buffer, nothing more enqueued), or one entry per slot: None
+    (pass-through), ``"deemphasis"`` (``deemphasis_sections()``), ``"voice"`` (``tone_strip_sections()``),
+    ``"voice+deemphasis"`` or an ``[S, 5]`` array of sections.  The chain then owns an ``AudioIirBank``
+    (``audio_iir``) that runs directly behind the demodulator bank on every call, with the demodulator
+    bank's own counts -- the ungated ones, so the stream stays continuous across closed gates -- into a
+    row tensor of its own; ``audio_filter=`` and ``pcm=`` then read those rows.  The tone and code meters
+    keep reading the demodulators' rows, and the reported counts, the gates and ``pcm()`` keep their
+    meaning.  ``audio_tensor`` and ``process`` return the last stage present.
+
     ``audio_filter``: None (no filter handle, no second audio buffer, nothing more enqueued), or one
     entry per slot: None (pass-through), ``"voice"`` (``voice_taps()``) or a 1-D float array of taps.
     The chain then owns an ``AudioFilterBank`` (``audio_fir``) that runs behind the demodulator bank
-    on every call with the demodulator bank's own counts (``audio_counts``) -- not the tone-gated
-    ones, so a slot's filtered stream is continuous across closed gates -- into a second row tensor,
-    which ``audio_tensor`` and ``process`` then return.  The tone meter keeps reading the
-    demodulators' rows: it needs the tone.  The reported counts stay as without the filter.
+    (behind the IIR bank with ``audio_iir=``) on every call with the demodulator bank's own counts
+    (``audio_counts``) -- not the tone-gated ones, so a slot's filtered stream is continuous across
+    closed gates -- into a second row tensor, which ``audio_tensor`` and ``process`` then return.  The
+    tone meter keeps reading the demodulators' rows: it needs the tone.  The reported counts stay as
+    without the filter.
 
     ``pcm``: None (no resampler handle, no PCM buffer, nothing more enqueued), an output rate in Hz, or a
     dict of ``AudioResamplerBank.for_rates`` keywords (``out_rate``, ``transition_hz``,
@@ -2170,6 +2398,7 @@ class _BankChain(_Chain):
     _pcm_counts = None
     _reported = None           # the last call's reported counts, kept only with pcm=
     _filtered = None           # the filter's rows; the handle is self.audio_fir, present only with audio_filter=
+    _iir_rows = None           # the IIR bank's rows; the handle is self.audio_iir, present only with audio_iir=
     _audio_counts = None
     _code = None               # the CodeRule; the meter handle is self.code_meter, present only with code=
     _tone = None               # the ToneRule; the meter handle is self.tone_meter, present only with tone=
@@ -2177,13 +2406,14 @@ class _BankChain(_Chain):
     _nominal = None            # (frequency, [channel frequencies]) of the user's set_frequencies
 
     def __init__(self, input_format: str, sample_rate: int, modes, rate: int, device: int, *front_args,
-                 squelch=None, afc=None, tone=None, audio_filter=None, pcm=None, code=None):
+                 squelch=None, afc=None, tone=None, audio_filter=None, pcm=None, code=None, audio_iir=None):
         import torch
 
         rule, self._afc_default_limit = _afc_rule(afc, modes, rate)
         probes = _tone_entries(tone, len(modes))
         codes = _code_entries(code, len(modes), None if probes is None else list(tone))
         filters = _audio_filter_entries(audio_filter, len(modes))
+        iirs = _audio_iir_entries(audio_iir, len(modes))
         resampler = _pcm_entry(pcm)
         self._torch = torch
         self.input_format, self.sample_rate, self.device = input_format, int(sample_rate), device
@@ -2218,6 +2448,11 @@ class _BankChain(_Chain):
                 for k, entry in enumerate(codes):
                     if entry is not None:
                         self._code.set_code(k, *entry)
+            if iirs is not None:
+                self.audio_iir = AudioIirBank(self._n_channels, device)
+                for k, sec in enumerate(iirs):
+                    if sec is not None:
+                        self.audio_iir.set_sections(k, sec)
             if filters is not None:
                 self.audio_fir = AudioFilterBank(self._n_channels, device)
                 for k, taps in enumerate(filters):
@@ -2352,8 +2587,11 @@ class _BankChain(_Chain):
 
     @property
     def audio_tensor(self):
-        """The rows of the last call: the filter's with ``audio_filter=``, else the demodulators'."""
-        return self._audio if self._filtered is None else self._filtered
+        """The rows of the last call, from the last stage present: the filter's with ``audio_filter=``,
+        else the IIR bank's with ``audio_iir=``, else the demodulators'."""
+        if self._filtered is not None:
+            return self._filtered
+        return self._audio if self._iir_rows is None else self._iir_rows
 
     @property
     def audio_counts(self):
@@ -2394,6 +2632,14 @@ class _BankChain(_Chain):
         if not 0 <= int(k) < self._n_channels:
             raise ValueError(f"slot {k} outside 0 ... {self._n_channels - 1}")
         fir.set_taps(int(k), _audio_filter_taps(entry))
+
+    def set_audio_iir(self, k: int, entry) -> None:
+        """Slot k's audio IIR from the next call on: None, a name or ``[S, 5]`` sections; its carry is zeroed."""
+        if not hasattr(self, "audio_iir"):
+            raise ValueError("this chain was built without an audio IIR (audio_iir=None)")
+        if not 0 <= int(k) < self._n_channels:
+            raise ValueError(f"slot {k} outside 0 ... {self._n_channels - 1}")
+        self.audio_iir.set_sections(int(k), _audio_iir_sections(entry))
 
     def _set_nominal(self, frequency: int, channel_frequencies) -> None:
         """After a user's ``set_frequencies`` went through: the rule starts again from these."""
@@ -2445,6 +2691,8 @@ class _BankChain(_Chain):
             self.tone_meter.set_stream(self.demods.stream)
         if self._code is not None:
             self.code_meter.set_stream(self.demods.stream)
+        if hasattr(self, "audio_iir"):
+            self.audio_iir.set_stream(self.demods.stream)
         if hasattr(self, "audio_fir"):
             self.audio_fir.set_stream(self.demods.stream)
         if hasattr(self, "audio_rs"):
@@ -2463,6 +2711,8 @@ class _BankChain(_Chain):
             self._re = torch.empty(shape, dtype=torch.float32, device=self._tdev)
             self._im = torch.empty(shape, dtype=torch.float32, device=self._tdev)
             self._audio = torch.empty(shape, dtype=torch.float32, device=self._tdev)
+            if hasattr(self, "audio_iir"):
+                self._iir_rows = torch.empty(shape, dtype=torch.float32, device=self._tdev)
             if hasattr(self, "audio_fir"):
                 self._filtered = torch.empty(shape, dtype=torch.float32, device=self._tdev)
             if hasattr(self, "audio_rs"):
@@ -2494,8 +2744,12 @@ class _BankChain(_Chain):
         counts = self.demods.process_device(self._re.data_ptr(), self._im.data_ptr(), cap, nq,
                                             self._audio.data_ptr(), cap)
         self._audio_counts = counts
+        voice = self._audio
+        if self._iir_rows is not None:
+            voice = self._iir_rows
+            self.audio_iir._call("process", self._audio.data_ptr(), cap, self.demods._counts, voice.data_ptr(), cap)
         if self._filtered is not None:
-            self.audio_fir._call("process", self._audio.data_ptr(), cap, self.demods._counts,
+            self.audio_fir._call("process", voice.data_ptr(), cap, self.demods._counts,
                                  self._filtered.data_ptr(), cap)
         if self._tone is not None:
             counts = self._step_tone(counts, cap)
@@ -2533,6 +2787,10 @@ class _BankChain(_Chain):
             self.code_meter.close()
             del self.code_meter
             self._code = None
+        if hasattr(self, "audio_iir"):
+            self.audio_iir.close()
+            del self.audio_iir
+            self._iir_rows = None
         if hasattr(self, "audio_fir"):
             self.audio_fir.close()
             del self.audio_fir
@@ -2555,10 +2813,10 @@ class ReceiverBank(_BankChain):
     Both stages are banked: a packet is 2 + 4 launches whatever the channel count."""
 
     def __init__(self, input_format: str, sample_rate: int, modes, device: int = 0, *, squelch=None, afc=None,
-                 tone=None, audio_filter=None, pcm=None, code=None):
+                 tone=None, audio_filter=None, pcm=None, code=None, audio_iir=None):
         self._cap_for = (None, 0)
         super().__init__(input_format, sample_rate, *_common_rate(modes), device, squelch=squelch, afc=afc, tone=tone,
-                         audio_filter=audio_filter, pcm=pcm, code=code)
+                         audio_filter=audio_filter, pcm=pcm, code=code, audio_iir=audio_iir)
 
     def _make_front(self):
         return FrontEndBank(self.input_format, self.sample_rate, self.quadrature_rate, self.n_channels, self.device,
@@ -2893,7 +3151,7 @@ class RasterReceiverBank(_BankChain):
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, channels=None, device: int = 0,
                  resample: bool = False, *, squelch=None, afc=None, tone=None, audio_filter=None, pcm=None,
-                 code=None):
+                 code=None, audio_iir=None):
         if afc is not None and afc is not False:
             raise ValueError("a RasterReceiverBank cannot tune: its prototype passes one raster channel per slot and "
                              "leaves no room to move; use a TunedReceiverBank for AFC")
@@ -2903,7 +3161,7 @@ class RasterReceiverBank(_BankChain):
             raise ValueError(f"{len(modes)} channels expected, got {len(channels)}")
         self._resample = bool(resample)
         super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, channels, squelch=squelch,
-                         tone=tone, audio_filter=audio_filter, pcm=pcm, code=code)
+                         tone=tone, audio_filter=audio_filter, pcm=pcm, code=code, audio_iir=audio_iir)
 
     def _make_front(self, spacing_hz: int, channels):
         make = Channelizer.for_raster_resampled if self._resample else Channelizer.for_raster
@@ -2940,14 +3198,14 @@ class TunedReceiverBank(_BankChain):
 
     def __init__(self, input_format: str, sample_rate: int, spacing_hz: int, modes, device: int = 0,
                  resample: bool = False, *, squelch=None, passband_hz: float | None = None, afc=None, tone=None,
-                 audio_filter=None, pcm=None, code=None):
+                 audio_filter=None, pcm=None, code=None, audio_iir=None):
         modes, rate = _common_rate(modes)
         if passband_hz is None:
             passband_hz = int(spacing_hz) / 2 + max(mode_info(m)[2] for m in modes)
         self.passband_hz = float(passband_hz)
         self._resample = bool(resample)
         super().__init__(input_format, sample_rate, modes, rate, device, spacing_hz, squelch=squelch, afc=afc,
-                         tone=tone, audio_filter=audio_filter, pcm=pcm, code=code)
+                         tone=tone, audio_filter=audio_filter, pcm=pcm, code=code, audio_iir=audio_iir)
 
     def _make_front(self, spacing_hz: int):
         front = Channelizer.for_channels(self.input_format, self.sample_rate, spacing_hz, self.quadrature_rate,
